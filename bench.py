@@ -14,6 +14,23 @@ timed region starts; the input buffer is read-only to the pipeline, so
 every step redoes identical work). value = records sorted per second,
 whole-job over all N ranks.
 
+A plain run does only what the headline figure needs: generate, warm up,
+time --steps steps, optionally --dump-outputs, print the result line.
+Everything below (per-run integrity checks, roofline, per-kernel
+breakdown, CPU baseline) runs only under --full and is null otherwise.
+
+--dump-outputs DIR writes what the last timed step returned, as float32 /
+float64 .npy files (the inputs are seeded and generated on-device, so two
+builds run with the same arguments are comparable output for output):
+  records_sample.npy   float32 (k, 100): the output records at a fixed,
+                       seeded set of k sorted positions (first and last
+                       record included)
+  sample_positions.npy float64 (k,): those positions
+  byte_column_sums.npy float64 (100,): per-byte-column sums over the WHOLE
+                       output (exact in float64; any changed byte moves one)
+  n_out.npy            float64 (1,): records in this rank's output
+(rank r > 0 of a distributed run writes <name>.rank<r>.npy.)
+
 The roofline object tracks the dominant kernel (the payload gather —
 out[i] = rec[idx[i]], ~45% of the step): achieved = algorithmic bytes per
 launch (2R + 4 = 204 B per record) / HIP-event-
@@ -44,6 +61,8 @@ REC = 100
 N_RECORDS_10GIB = 10 * GIB // REC          # 107,374,182
 SEED = 0x7421
 PEAK_HBM_GBS = 8000.0                      # MI355X_MICROARCH.md spec peak
+DUMP_SAMPLE = 65536                        # records sampled by --dump-outputs
+DUMP_SEED = 0xD0A7
 
 
 def log(msg):
@@ -58,7 +77,15 @@ def parse_args():
     ap.add_argument("--records", type=int, default=N_RECORDS_10GIB)
     ap.add_argument("--seed", type=int, default=SEED)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the integrity checks, the roofline / "
+                         "per-kernel measurement pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def validate(ts, d_out, n_out):
@@ -141,7 +168,82 @@ def main():
     log(f"rank {rank}/{world}: generated {ts.n_local} records "
         f"({ts.n_local * REC / GIB:.2f} GiB) seed={hex(args.seed)}")
 
-    # input key-sum for conservation check
+    in_keysum = input_keysum(ts) if args.full else None
+
+    for _ in range(args.warmup):
+        ts.step()
+    torch.cuda.synchronize()
+
+    perf_breakdown, roofline = roofline_leg(ts) if args.full \
+        else (None, None)
+
+    # timed region
+    if dist:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        out, n_out = ts.step()
+    if dist:
+        dist.barrier()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    if dist:
+        ctl = "cpu" if dist.get_backend() == "gloo" else "cuda"
+        t = torch.tensor([elapsed], device=ctl)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, n_out, rank, world)
+
+    if args.full:
+        check_output(ts, out, n_out, in_keysum, dist, rank, world)
+
+    ms_per_step = elapsed / args.steps * 1e3
+    value = n_total * args.steps / elapsed
+
+    cpu_baseline = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        log("timing CPU baseline (oracle, bounded sample)...")
+        cpu_baseline = cpu_baseline_leg(args.seed, n_total)
+
+    if rank == 0:
+        result = {
+            "metric": "TeraSort keys/sec (100-byte recs)",
+            "value": round(value, 1),
+            "unit": "keys/s",
+            "n_gpus": args.gpus,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 2),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic",
+            "config": {
+                "workload": "terasort_10GiB_100B",
+                "records": n_total,
+                "record_bytes": REC,
+                "seed": hex(args.seed),
+                "parallelism": f"dp{args.gpus}",
+            },
+            "roofline": roofline,
+            "cpu_baseline": cpu_baseline,
+            "perf_breakdown": perf_breakdown,
+            "validated": {"keysum_conserved": True, "sorted": True}
+            if args.full else None,
+        }
+        print(json.dumps(result), flush=True)
+
+    ts.close()
+    if dist:
+        dist.destroy_process_group()
+
+
+def input_keysum(ts):
+    """input key-sum for the conservation check"""
     dk = torch.empty(ts.n_local, dtype=torch.int64, device="cuda")
     di = torch.empty(ts.n_local, dtype=torch.int32, device="cuda")
     ts.nat.extract_key64(ctypes.c_void_p(ts.d_in.data_ptr()), ts.n_local,
@@ -149,14 +251,44 @@ def main():
                          ctypes.c_void_p(di.data_ptr()),
                          ctypes.c_void_p(
                              torch.cuda.current_stream().cuda_stream))
-    in_keysum = int(dk.sum().item())
-    del dk, di
+    return int(dk.sum().item())
 
-    for _ in range(args.warmup):
-        ts.step()
-    torch.cuda.synchronize()
 
-    # roofline measurement pass (untimed, events on the product stream)
+def dump_outputs(out_dir, out, n_out, rank, world):
+    """Write what the last timed step returned (see the module docstring).
+    Torch here only reads the finished output back; at most ~27 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    recs = out[:n_out * REC].view(n_out, REC)
+    k = min(n_out, DUMP_SAMPLE // world)
+    pos = np.zeros(0, dtype=np.int64)
+    if k:
+        rng = np.random.default_rng(DUMP_SEED)
+        pos = np.unique(np.concatenate(
+            [[0, n_out - 1], rng.integers(0, n_out, k - min(k, 2))]))
+    sample = np.zeros((len(pos), REC), dtype=np.uint8)
+    colsum = torch.zeros(REC, dtype=torch.int64, device="cuda")
+    chunk = 1 << 24     # records; keeps every torch op under 2^31 bytes
+    for lo in range(0, n_out, chunk):
+        part = recs[lo:lo + chunk]
+        colsum += part.sum(dim=0, dtype=torch.int64)
+        a, b = np.searchsorted(pos, [lo, lo + chunk])
+        if b > a:
+            sample[a:b] = part[torch.from_numpy(pos[a:b] - lo).cuda()] \
+                .cpu().numpy()
+    sfx = "" if rank == 0 else f".rank{rank}"
+    for name, arr in [
+            ("records_sample", sample.astype(np.float32)),
+            ("sample_positions", pos.astype(np.float64)),
+            ("byte_column_sums", colsum.cpu().numpy().astype(np.float64)),
+            ("n_out", np.array([n_out], dtype=np.float64))]:
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
+    log(f"rank {rank}: wrote {len(pos)} sampled records + column sums to "
+        f"{out_dir}")
+
+
+def roofline_leg(ts):
+    """roofline measurement pass (untimed, events on the product stream).
+    Returns (perf_breakdown, roofline)."""
     ts.nat.perf_reset()
     ts.nat.perf_enable(True)
     out, n_out = ts.step()
@@ -222,24 +354,11 @@ def main():
             "avg_launch_ms": round(g_ms / g_n, 3),
         }
 
-    # timed region
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out, n_out = ts.step()
-    if dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    if dist:
-        ctl = "cpu" if dist.get_backend() == "gloo" else "cuda"
-        t = torch.tensor([elapsed], device=ctl)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+    return perf_breakdown, roofline
 
-    # validation
+
+def check_output(ts, out, n_out, in_keysum, dist, rank, world):
+    """--full: integrity checks of the last timed step's output."""
     keysum, mono, first, last = validate(ts, out, n_out)
     if dist:
         ctl = "cpu" if dist.get_backend() == "gloo" else "cuda"
@@ -258,46 +377,6 @@ def main():
                     assert fl[r][0] >= fl[r - 1][1], f"boundary {r}"
     assert mono, "output key prefixes not sorted"
     assert keysum == in_keysum, "key-sum conservation failed"
-
-    ms_per_step = elapsed / args.steps * 1e3
-    value = n_total * args.steps / elapsed
-
-    cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        log("timing CPU baseline (oracle, bounded sample)...")
-        cpu_baseline = cpu_baseline_leg(args.seed, n_total)
-
-    if rank == 0:
-        result = {
-            "metric": "TeraSort keys/sec (100-byte recs)",
-            "value": round(value, 1),
-            "unit": "keys/s",
-            "n_gpus": args.gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 2),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": "terasort_10GiB_100B",
-                "records": n_total,
-                "record_bytes": REC,
-                "seed": hex(args.seed),
-                "parallelism": f"dp{args.gpus}",
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu_baseline,
-            "perf_breakdown": perf_breakdown,
-            "validated": {"keysum_conserved": True, "sorted": True},
-        }
-        print(json.dumps(result), flush=True)
-
-    ts.close()
-    if dist:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
