@@ -116,6 +116,20 @@ int t9_sort_records_keyle(t9_context* ctx, const uint8_t* d_in,
                           uint8_t* d_out, uint64_t n, uint32_t rec_size,
                           void* d_workspace, void* stream);
 
+/* How the last t9_sort_records / t9_sort_records_keyle call on ctx was
+ * scheduled: 0 = serial (sort everything, then gather), otherwise the
+ * number of non-empty chunks whose payload gather ran on the context's
+ * internal stream while later sub-buckets were still being sorted (100-byte
+ * records on the two-level 9-bit MSB flow with no oversize sub-bucket).
+ * The overlapped schedule is OFF by default — measured slower than serial
+ * on MI355X — T9_SORT_OVERLAP=1 enables it, =0 forces serial,
+ * T9_SORT_OVERLAP_CHUNKS sets the chunk count (default 8, at most 16).
+ * The internal stream and its events belong to the
+ * context (created on first use, freed by t9_destroy) and are ordered
+ * against `stream` by events on both sides, so the call's stream contract
+ * is unchanged. A context is driven by ONE host thread at a time. */
+int t9_sort_last_schedule(const t9_context* ctx);
+
 /* ------------------------------------------------------------------ *
  * Classification + partition — replaces TransmitItems' tree-descent loop
  * (thrill/api/sort.hpp:434-535). bucket(item i) = #{ j : (splitter_key[j],

@@ -31,6 +31,10 @@ int t9_create(t9_context** out, int device, int rank, int world,
     ctx->world = world;
     ctx->comm = comm;
     ctx->owns_comm = 0;
+    ctx->ov_stream = nullptr;
+    for (int i = 0; i <= T9_OVERLAP_MAXK; ++i) ctx->ov_ev[i] = nullptr;
+    ctx->ov_ready = 0;
+    ctx->last_schedule = 0;
     *out = ctx;
     return T9_OK;
 }
@@ -38,8 +42,40 @@ int t9_create(t9_context** out, int device, int rank, int world,
 int t9_destroy(t9_context* ctx) {
     if (ctx && ctx->comm && ctx->owns_comm)
         ncclCommDestroy((ncclComm_t)ctx->comm);
+    if (ctx) {
+        /* the join of the last overlapped sort already ordered the
+         * internal stream before the caller's; drain it anyway */
+        if (ctx->ov_stream) {
+            (void)hipStreamSynchronize(ctx->ov_stream);
+            (void)hipStreamDestroy(ctx->ov_stream);
+        }
+        for (int i = 0; i <= T9_OVERLAP_MAXK; ++i)
+            if (ctx->ov_ev[i]) (void)hipEventDestroy(ctx->ov_ev[i]);
+    }
     delete ctx;
     return T9_OK;
+}
+
+/* internal: lazily create the overlap stream + events (sort_msb_impl) */
+int t9i_overlap_init(t9_context* ctx) {
+    if (!ctx) return T9_EINVAL;
+    if (ctx->ov_ready) return T9_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* non-blocking: the caller's stream may be the legacy default stream,
+     * which would serialise against a blocking stream */
+    if (!ctx->ov_stream)
+        HIP_TRY(hipStreamCreateWithFlags(&ctx->ov_stream,
+                                         hipStreamNonBlocking));
+    for (int i = 0; i <= T9_OVERLAP_MAXK; ++i)
+        if (!ctx->ov_ev[i])
+            HIP_TRY(hipEventCreateWithFlags(&ctx->ov_ev[i],
+                                            hipEventDisableTiming));
+    ctx->ov_ready = 1;
+    return T9_OK;
+}
+
+int t9_sort_last_schedule(const t9_context* ctx) {
+    return ctx ? ctx->last_schedule : T9_EINVAL;
 }
 
 /* ------------------------------------------------------------------ *

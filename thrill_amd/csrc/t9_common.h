@@ -41,12 +41,35 @@ using u64 = uint64_t;
         }                                                                 \
     } while (0)
 
+#define T9_OVERLAP_MAXK 16   /* most chunks of the sort -> gather pipeline */
+
 struct t9_context {
     int device;
     int rank;
     int world;
     void* comm;     /* ncclComm_t or nullptr */
     int owns_comm;  /* 1 if t9_comm_init created it (t9_destroy frees) */
+    /* sort -> gather overlap (sort_msb_impl): internal non-blocking
+     * stream, one event per chunk plus the join event; created on first
+     * use, freed by t9_destroy */
+    hipStream_t ov_stream;
+    hipEvent_t ov_ev[T9_OVERLAP_MAXK + 1];
+    int ov_ready;
+    int last_schedule;   /* t9_sort_last_schedule */
+};
+
+/* record-sort request riding along the pair sort: when the two-level
+ * 9-bit MSB flow can, it gathers out[a..b) = recs[idx[a..b)] chunk by
+ * chunk on the context's internal stream while later sub-buckets are
+ * still being sorted, and counts equal-prefix neighbours into d_ntied
+ * (zeroed by the sort). chunks stays 0 when the serial schedule ran —
+ * then the caller counts ties and gathers itself. */
+struct t9_overlap_req {
+    const u8* recs;
+    u8* out;
+    u32 rec_words;
+    u32* d_ntied;
+    u32 chunks;   /* out: non-empty chunks gathered on the internal stream */
 };
 
 /* splitmix64 random access — must match oracle/t9_oracle.cpp splitmix64_at */

@@ -76,8 +76,12 @@ __device__ inline void t9_hist_ballot_add(u32* __restrict__ s_cnt, u32 d,
  * is built from the record bytes and the payload is the record index
  * (iota), eliminating the separate extract pass and the packed key-array
  * round trip for MSB pass 1. */
+/* IOTA_VAL: the payload of element base + i is (u32)(base + i) as in the
+ * REC_WORDS mode, but the keys are the packed u64 array — pass 1 after the
+ * fused extract + histogram, which then need not write the index iota
+ * for this kernel to read back (in_vals is not touched). */
 template <int TILE, int BLOCK, bool HAS_KEY, bool HAS_VAL,
-          int REC_WORDS = 0>
+          int REC_WORDS = 0, bool IOTA_VAL = false>
 __global__ __launch_bounds__(BLOCK, 4) void k_scatter_wave512(
     const u64* __restrict__ in_keys, const u32* __restrict__ in_vals,
     u64* __restrict__ out_keys, u32* __restrict__ out_vals,
@@ -166,7 +170,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_scatter_wave512(
             if (HAS_KEY) s_okeys[pos] = k;
             if (HAS_VAL)
                 s_ovals[pos] =
-                    REC_WORDS ? (u32)(base + i) : in_vals[base + i];
+                    (REC_WORDS || IOTA_VAL) ? (u32)(base + i)
+                                            : in_vals[base + i];
             s_digof[pos] = (u8)d;
         }
     }

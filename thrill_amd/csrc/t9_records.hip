@@ -25,7 +25,7 @@ extern "C" u64 t9_partition_idx_workspace(u64 n);
 extern "C" int t9_partition_idx(t9_context*, const u32*, u64, u32, u32*,
                                 u64*, void*, void*);
 extern "C" int t9i_sort_pairs_msb_ph(t9_context*, u64*, u32*, u64, void*,
-                                     void*);
+                                     void*, int, t9_overlap_req*);
 extern "C" u32* t9i_msb_pass1_hist(void* d_workspace, u64 n);
 
 /* ------------------------------------------------------------------ */
@@ -147,7 +147,12 @@ __global__ __launch_bounds__(256) void k_gather_records(
 template <int RW, bool NT>
 __global__ __launch_bounds__(256) void k_gather_records_span(
     const u8* __restrict__ recs, const u32* __restrict__ idx, u64 n,
-    u32 rec_words_rt, u8* __restrict__ out) {
+    u32 rec_words_rt, u8* __restrict__ out,
+    const u32* __restrict__ abort_flag) {
+    /* speculative launches (chunked sort -> gather pipeline) point this at
+     * the tie counter: once a tie is known the output will be redone, so
+     * the block has nothing useful to do. nullptr: always run. */
+    if (abort_flag && *abort_flag) return;
     const u32 rec_words = RW ? (u32)RW : rec_words_rt;
     const u64 total_words = n * rec_words;
     const u64 span = (total_words + gridDim.x - 1) / gridDim.x;
@@ -471,7 +476,9 @@ __global__ __launch_bounds__(256) void k_zipf_tokens(
  * counts come out of the same pass, eliminating the separate pass-1
  * histogram read (k_hist_msb). Output layout identical to
  * k_extract_key64 + k_hist_msb<0> at shift 56. */
-template <int RW, bool LE, bool DB = true>
+/* IDX = false: the index iota is not written — the pass-1 scatter that
+ * follows produces it itself (k_scatter_wave512 IOTA_VAL). */
+template <int RW, bool LE, bool DB = true, bool IDX = true>
 __global__ __launch_bounds__(256) void k_extract_hist(
     const u8* __restrict__ recs, u64 n, u64* __restrict__ keys,
     u32* __restrict__ idx, u32* __restrict__ hist) {
@@ -521,12 +528,35 @@ __global__ __launch_bounds__(256) void k_extract_hist(
                     __builtin_bswap32(s_buf[cur][tid * RW + 1]);
             const u64 gi = tile0 + s0 + tid;
             keys[gi] = k;
-            idx[gi] = (u32)gi;
+            if (IDX) idx[gi] = (u32)gi;
         }
         t9_hist_ballot_add<8>(s_cnt, (u32)(k >> 56), valid, tid & 63);
         __syncthreads();
     }
     hist[(u64)blockIdx.x * 256 + tid] = s_cnt[tid];
+}
+
+/* the fused extract + pass-1 histogram launch ladder; IDX = false leaves
+ * the index iota to the pass-1 scatter */
+template <bool IDX>
+static void launch_extract_hist(u32 rw, bool le, bool sb, u32 B,
+                                hipStream_t s, const u8* d_in, u64 n,
+                                u64* d_keys, u32* d_idx, u32* hist) {
+    if (rw == 25 && !le && sb)
+        hipLaunchKernelGGL((k_extract_hist<25, false, false, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else if (rw == 25 && !le)
+        hipLaunchKernelGGL((k_extract_hist<25, false, true, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else if (rw == 25)
+        hipLaunchKernelGGL((k_extract_hist<25, true, true, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else if (!le)
+        hipLaunchKernelGGL((k_extract_hist<32, false, true, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else
+        hipLaunchKernelGGL((k_extract_hist<32, true, true, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
 }
 
 /* scatter-records experiment (gather-wall probe): read the input
@@ -684,11 +714,11 @@ int t9_gather_records(t9_context* ctx, const u8* d_recs, const u32* d_idx,
         else if (rw == 25 && var == 3)
             hipLaunchKernelGGL((k_gather_records_span<25, false>), grid,
                                dim3(256), 0, s, d_recs, d_idx, n, rw,
-                               d_out);
+                               d_out, (const u32*)nullptr);
         else if (rw == 25 && var == 4)
             hipLaunchKernelGGL((k_gather_records_span<25, true>), grid,
                                dim3(256), 0, s, d_recs, d_idx, n, rw,
-                               d_out);
+                               d_out, (const u32*)nullptr);
         else if (rw == 32)
             hipLaunchKernelGGL((k_gather_records<32, false>), grid,
                                dim3(256), 0, s, d_recs, d_idx, n, rw,
@@ -701,6 +731,25 @@ int t9_gather_records(t9_context* ctx, const u8* d_recs, const u32* d_idx,
             hipLaunchKernelGGL((k_gather_records<0, false>), grid,
                                dim3(256), 0, s, d_recs, d_idx, n, rw,
                                d_out));
+    T9_LAUNCH_CHECK();
+    return T9_OK;
+}
+
+/* internal: one chunk of the chunked sort -> gather pipeline
+ * (sort_msb_impl): the span gather over n 100-byte records of a total of
+ * n_total, with the grid scaled from the full launch's cap in proportion
+ * to the chunk, so a block's span stays what the tuning measured. */
+int t9i_gather_chunk(const u8* d_recs, const u32* d_idx, u64 n, u64 n_total,
+                     u8* d_out, const u32* d_abort, hipStream_t s) {
+    if (n == 0) return T9_OK;
+    const char* gg = getenv("T9_GATHER_GRID");
+    const u64 gcap = gg ? (u64)atoi(gg) : 16384;
+    u64 cap = t9_ceil_div(gcap * n, n_total ? n_total : 1);
+    if (cap < 1) cap = 1;
+    const u64 want = t9_ceil_div(n * 25, 256);
+    const dim3 grid((u32)((want < cap) ? want : cap));
+    hipLaunchKernelGGL((k_gather_records_span<25, false>), grid, dim3(256),
+                       0, s, d_recs, d_idx, n, 25u, d_out, d_abort);
     T9_LAUNCH_CHECK();
     return T9_OK;
 }
@@ -804,6 +853,8 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
     bool fused = fe && atoi(fe) && n >= (1ull << 14) &&
                  (rec_size == 100 || rec_size == 128);
     int rc;
+    t9_overlap_req ov = { nullptr, nullptr, 0, nullptr, 0 };
+    if (ctx) ctx->last_schedule = 0;
     if (eh && !fused) {
         u32* hist = t9i_msb_pass1_hist(pair_ws, n);
         const u64 B = t9_ceil_div(n, 8192);
@@ -812,31 +863,32 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
            barrier; T9_EXTRACT_SB=0 restores double buffering */
         const char* sbe = getenv("T9_EXTRACT_SB");
         const bool sb = !(sbe && sbe[0] == '0');
-        T9_PERF_WRAP(
-            s, "extract",
-            if (rw == 25 && !le && sb)
-                hipLaunchKernelGGL((k_extract_hist<25, false, false>),
-                                   dim3((u32)B), dim3(256), 0, s, d_in, n,
-                                   d_keys, d_idx, hist);
-            else if (rw == 25 && !le)
-                hipLaunchKernelGGL((k_extract_hist<25, false>),
-                                   dim3((u32)B), dim3(256), 0, s, d_in, n,
-                                   d_keys, d_idx, hist);
-            else if (rw == 25)
-                hipLaunchKernelGGL((k_extract_hist<25, true>),
-                                   dim3((u32)B), dim3(256), 0, s, d_in, n,
-                                   d_keys, d_idx, hist);
-            else if (!le)
-                hipLaunchKernelGGL((k_extract_hist<32, false>),
-                                   dim3((u32)B), dim3(256), 0, s, d_in, n,
-                                   d_keys, d_idx, hist);
-            else
-                hipLaunchKernelGGL((k_extract_hist<32, true>),
-                                   dim3((u32)B), dim3(256), 0, s, d_in, n,
-                                   d_keys, d_idx, hist));
+        /* the pass-1 scatter produces the index iota itself, so the
+         * extract need not write it (0.43 GB written + 0.43 GB read back
+         * at the 10 GiB bench); T9_EXTRACT_IOTA=1 restores the round trip */
+        const char* ie = getenv("T9_EXTRACT_IOTA");
+        const bool widx = ie && ie[0] == '1';
+        T9_PERF_WRAP(s, "extract",
+                     if (widx) launch_extract_hist<true>(
+                         rw, le, sb, (u32)B, s, d_in, n, d_keys, d_idx,
+                         hist);
+                     else launch_extract_hist<false>(
+                         rw, le, sb, (u32)B, s, d_in, n, d_keys, d_idx,
+                         hist));
         T9_LAUNCH_CHECK();
-        rc = t9i_sort_pairs_msb_ph(ctx, d_keys, d_idx, n, pair_ws,
-                                   stream);
+        /* 100-byte records through the default span gather may be
+         * gathered chunk by chunk while the sub-bucket sort is still
+         * running (sort_msb_impl decides; ov.chunks says what ran) */
+        const char* gv = getenv("T9_GATHER_VARIANT");
+        const bool may_overlap = rw == 25 && ctx && !(gv && atoi(gv) != 3);
+        if (may_overlap) {
+            ov.recs = d_in;
+            ov.out = d_out;
+            ov.rec_words = rw;
+            ov.d_ntied = d_ntied;
+        }
+        rc = t9i_sort_pairs_msb_ph(ctx, d_keys, d_idx, n, pair_ws, stream,
+                                   widx ? 0 : 1, may_overlap ? &ov : nullptr);
     }
     else if (fused && !le) {
         rc = t9i_sort_recs_msb(ctx, d_in, rec_size, d_keys, d_idx, n,
@@ -851,11 +903,23 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
         rc = t9_sort_pairs_u64_u32(ctx, d_keys, d_idx, n, pair_ws, stream);
     }
     if (rc) return rc;
-    rc = t9i_count_tied(d_keys, n, d_ntied, s);
-    if (rc) return rc;
+    /* overlapped schedule: ties are already counted chunk by chunk and
+     * the caller's stream has joined the internal one */
+    if (!ov.chunks) {
+        rc = t9i_count_tied(d_keys, n, d_ntied, s);
+        if (rc) return rc;
+    }
     u32 ntied = 0;
     HIP_TRY(hipMemcpyAsync(&ntied, d_ntied, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (ov.chunks) {
+        ctx->last_schedule = (int)ov.chunks;
+        /* no tie: every chunk's gather ran to the end (d_ntied only
+         * grows, so none saw the abort flag) and d_out is complete. With
+         * ties the speculative writes into d_out are finished (join) and
+         * the tie machinery + full gather below redo it. */
+        if (!ntied) return T9_OK;
+    }
 
     if (ntied && rec_size > 8) {
         /* on-device tie sort (kernels + plan above k_tie_flags). Scratch

@@ -1017,11 +1017,64 @@ u64 msb_ws_bytes(u64 n) {
 
 extern "C" u64 t9i_sort_pairs_msb_workspace(u64 n) { return msb_ws_bytes(n); }
 
+/* ---- chunked sort -> gather pipeline (record sort, 9-bit flow) ------ *
+ * After level 2 every sub-bucket sits at its final compact position, so
+ * out[a..b) depends on idx[a..b) alone. The wave16 sub-sort is bound by
+ * block slots and the LDS pipe and leaves HBM nearly idle; the payload
+ * gather is bound by HBM and leaves the LDS pipe idle. The NSUB9
+ * sub-buckets are cut into K contiguous ranges: the caller's stream sorts
+ * range c, counts its equal-prefix neighbours and records an event; the
+ * context's internal stream waits for it and gathers the records of range
+ * c while the caller's stream is already sorting range c + 1. All
+ * ordering is by stream events.
+ *
+ * DEFAULT OFF (T9_SORT_OVERLAP=1 enables, T9_SORT_OVERLAP_CHUNKS
+ * overrides K): measured at the 10 GiB bench the two kernels do run
+ * together, but the step gets SLOWER (15.85 vs 14.21 ms at K = 8; K = 2,
+ * 4, 16 and either queue priority are no better). Co-running, a sort
+ * chunk stretches from 0.37 to 1.36 ms and a gather chunk from 0.94 to
+ * 1.38 ms — more than the two back to back: the gather's rate comes from
+ * having every wave slot full of outstanding random loads, and the sort's
+ * blocks take those slots. DESIGN.md negative-results ledger,
+ * profiles/r03_overlap_kernel_trace.txt. */
+extern "C" int t9i_overlap_init(t9_context* ctx);
+extern "C" int t9i_count_tied_acc(const u64*, u64, u32*, hipStream_t);
+extern "C" int t9i_gather_chunk(const u8*, const u32*, u64, u64, u8*,
+                                const u32*, hipStream_t);
+
+#define T9_OVERLAP_K 8   /* least slow of 2/4/8/16 */
+
+static u32 overlap_chunks() {
+    const char* on = getenv("T9_SORT_OVERLAP");
+    if (!on || on[0] == '0' || on[0] == '\0') return 0;
+    const char* e = getenv("T9_SORT_OVERLAP_CHUNKS");
+    int k = e ? atoi(e) : T9_OVERLAP_K;
+    if (k < 1) k = 1;
+    if (k > T9_OVERLAP_MAXK) k = T9_OVERLAP_MAXK;
+    return (u32)k;
+}
+
+/* out[0..1] = info[0..1] (k_subinfo's max and oversize count), out[1 + c]
+ * = first record of chunk c (c = 1..K-1): one read-back fetches all.
+ * sub_start is a running exclusive sum over the sub-buckets (k_seg_scan9:
+ * compact bucket base + exclusive digit scan), so it is monotone across
+ * empty sub-buckets and an entry is the chunk's record boundary as is. */
+__global__ __launch_bounds__(64) void k_chunk_bounds(
+    const u32* __restrict__ sub_start, u32 nsub, u32 K,
+    const u32* __restrict__ info, u32* __restrict__ out) {
+    const u32 c = threadIdx.x;
+    if (c < 2) out[c] = info[c];
+    if (c >= 1 && c < K)
+        out[1 + c] = sub_start[(u64)c * nsub / K];
+}
+
 template <bool HAS_VAL, int RW = 0>
 static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                          u64* d_keys, u32* d_vals, u64 n,
                          void* d_workspace, void* stream,
-                         bool pre_hist = false) {
+                         bool pre_hist = false,
+                         t9_overlap_req* ov = nullptr,
+                         bool iota_vals = false) {
     hipStream_t s = (hipStream_t)stream;
     MsbWs w = carve_msb((char*)d_workspace, n);
 
@@ -1047,10 +1100,18 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                            w.hist, B, w.chunkpart, w.abase);
         T9_PERF_WRAP(
             s, "pair_scatter",
-            hipLaunchKernelGGL(
-                (k_scatter_wave512<T9_MSB_TILE, 1024, true, HAS_VAL, RW>),
-                dim3((u32)B), dim3(1024), 0, s, pass1_src, d_vals, w.alt_k,
-                w.alt_v, w.hist, n, 56));
+            if (HAS_VAL && !RW && iota_vals)
+                hipLaunchKernelGGL(
+                    (k_scatter_wave512<T9_MSB_TILE, 1024, true, HAS_VAL, 0,
+                                       true>),
+                    dim3((u32)B), dim3(1024), 0, s, pass1_src, d_vals,
+                    w.alt_k, w.alt_v, w.hist, n, 56);
+            else
+                hipLaunchKernelGGL(
+                    (k_scatter_wave512<T9_MSB_TILE, 1024, true, HAS_VAL,
+                                       RW>),
+                    dim3((u32)B), dim3(1024), 0, s, pass1_src, d_vals,
+                    w.alt_k, w.alt_v, w.hist, n, 56));
         T9_LAUNCH_CHECK();
     }
 
@@ -1077,11 +1138,70 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
             hipLaunchKernelGGL(k_subinfo, dim3((u32)(NSUB9 / 256)),
                                dim3(256), 0, s, w.sub_n, (u32)NSUB9,
                                T9_SUBMAX, NSUB, w.ovr, w.ovr + 2);
-            u32 info[2] = { 0, 0 };
-            HIP_TRY(hipMemcpyAsync(info, w.ovr, 8, hipMemcpyDeviceToHost,
-                                   s));
+            /* a record sort that may overlap its gather fetches the chunk
+             * boundaries in this same read-back (w.span is free in the
+             * 9-bit flow) */
+            const u32 K = (HAS_VAL && ov && ctx && !t9perf_on() &&
+                           t9i_lds_wave16())
+                              ? overlap_chunks() : 0;
+            u32 info[2 + T9_OVERLAP_MAXK] = { 0, 0 };
+            if (K) {
+                hipLaunchKernelGGL(k_chunk_bounds, dim3(1), dim3(64), 0, s,
+                                   w.sub_start, (u32)NSUB9, K, w.ovr,
+                                   w.span);
+                HIP_TRY(hipMemcpyAsync(info, w.span, (K + 1) * 4,
+                                       hipMemcpyDeviceToHost, s));
+            }
+            else
+                HIP_TRY(hipMemcpyAsync(info, w.ovr, 8,
+                                       hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             const u32 maxsub = info[0], novr9 = info[1];
+            if (K && novr9 == 0 && maxsub <= t9i_wave16_max()) {
+                u64 bnd[T9_OVERLAP_MAXK + 1];
+                bnd[0] = 0;
+                bnd[K] = n;
+                bool mono = true;
+                for (u32 c = 1; c < K; ++c) {
+                    bnd[c] = info[1 + c];
+                    mono = mono && bnd[c] >= bnd[c - 1] && bnd[c] <= n;
+                }
+                if (mono) {
+                    int rc = t9i_overlap_init(ctx);
+                    if (rc) return rc;
+                    hipStream_t sb = ctx->ov_stream;
+                    HIP_TRY(hipMemsetAsync(ov->d_ntied, 0, 4, s));
+                    u32 done = 0;
+                    for (u32 c = 0; c < K; ++c) {
+                        const u64 a = bnd[c], b = bnd[c + 1];
+                        if (a == b) continue;   /* empty chunk */
+                        const u32 sub0 = (u32)((u64)c * NSUB9 / K);
+                        const u32 sub1 = (u32)((u64)(c + 1) * NSUB9 / K);
+                        t9i_launch_wave16_sub<HAS_VAL>(
+                            sub1 - sub0, maxsub, s, d_keys, d_vals,
+                            w.sub_start + sub0, w.sub_n + sub0);
+                        T9_LAUNCH_CHECK();
+                        /* no comparison across the chunk edge: adjacent
+                         * sub-buckets differ in their top 17 key bits */
+                        rc = t9i_count_tied_acc(d_keys + a, b - a,
+                                                ov->d_ntied, s);
+                        if (rc) return rc;
+                        HIP_TRY(hipEventRecord(ctx->ov_ev[c], s));
+                        HIP_TRY(hipStreamWaitEvent(sb, ctx->ov_ev[c], 0));
+                        rc = t9i_gather_chunk(
+                            ov->recs, d_vals + a, b - a, n,
+                            ov->out + a * (u64)ov->rec_words * 4,
+                            ov->d_ntied, sb);
+                        if (rc) return rc;
+                        ++done;
+                    }
+                    HIP_TRY(hipEventRecord(ctx->ov_ev[T9_OVERLAP_MAXK], sb));
+                    HIP_TRY(hipStreamWaitEvent(
+                        s, ctx->ov_ev[T9_OVERLAP_MAXK], 0));
+                    ov->chunks = done;
+                    return T9_OK;
+                }
+            }
             T9_PERF_WRAP(
                 s, "lds_sort",
                 if (t9i_lds_wave16() && maxsub <= t9i_wave16_max())
@@ -1390,12 +1510,17 @@ extern "C" int t9i_sort_pairs_msb(t9_context* ctx, u64* d_keys,
 
 /* pre-hist variant: the caller (fused extract, t9_records.hip) already
  * wrote the pass-1 byte-7 histogram rows into the workspace slot
- * returned by t9i_msb_pass1_hist */
+ * returned by t9i_msb_pass1_hist. iota_vals: d_vals holds nothing yet —
+ * the payload is the element's index and pass 1 produces it. ov (may be
+ * null): record-sort request that may run the chunked sort -> gather
+ * pipeline (ov->chunks != 0 on return: output gathered, ties counted
+ * into ov->d_ntied, caller's stream joined). */
 extern "C" int t9i_sort_pairs_msb_ph(t9_context* ctx, u64* d_keys,
                                      u32* d_vals, u64 n,
-                                     void* d_workspace, void* stream) {
+                                     void* d_workspace, void* stream,
+                                     int iota_vals, t9_overlap_req* ov) {
     return sort_msb_impl<true>(ctx, d_keys, d_keys, d_vals, n, d_workspace,
-                               stream, true);
+                               stream, true, ov, iota_vals != 0);
 }
 
 extern "C" u32* t9i_msb_pass1_hist(void* d_workspace, u64 n) {

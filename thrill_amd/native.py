@@ -52,6 +52,7 @@ _SIGS = {
     "t9_sort_records_workspace": (u64, [u64, u32]),
     "t9_sort_records": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
     "t9_sort_records_keyle": (i32, [vp, vp, vp, u64, u32, vp, vp]),
+    "t9_sort_last_schedule": (i32, [vp]),
     "t9_extract_key64_le": (i32, [vp, vp, u64, u32, u32, vp, vp, vp]),
     "t9_classify_u64": (i32, [vp, vp, u64, u64, vp, vp, u32, vp, vp, vp]),
     "t9_classify_rec": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, u32, u32,
@@ -127,6 +128,14 @@ class Native:
         rc = self._lib.t9_comm_init(self.ctx, buf)
         if rc != 0:
             raise T9Error(f"t9_comm_init failed rc={rc}")
+
+    def sort_last_schedule(self):
+        """0 = the last record sort ran serially; k > 0 = k chunks were
+        gathered on the internal stream, overlapped with the sub sort."""
+        k = self._lib.t9_sort_last_schedule(self.ctx)
+        if k < 0:
+            raise T9Error(f"t9_sort_last_schedule failed rc={k}")
+        return k
 
     # perf registry functions take no context argument
     def perf_enable(self, on):
