@@ -21,6 +21,10 @@
  * generic ReduceByKey for (string, u64-counter) pairs that
  * dictionary-encodes words and reduces on the GPU 128-bit composite
  * table (string identity — DESIGN.md "Config-4 string identity").
+ *
+ * TextWordCount takes raw text bytes instead: tokenizing, hashing,
+ * reducing and choosing one spelling per word all run on the device
+ * (DESIGN.md "Real text: device tokenizer and hasher").
  */
 #pragma once
 
@@ -776,6 +780,123 @@ DIA<ValueType> DIA<ValueType>::ReduceByKey(const KeyExtractor& key_ex,
         for (auto& kv : acc) out.push_back(kv.second);
     }
     return FromVector(*ctx_, out);
+}
+
+//! TextWordCount — word_count over raw text bytes with the whole PreOp on
+//! the device: ReadLines + the WordCount split (a word is a maximal run of
+//! bytes other than ' ' and '\n'), the string_hash2 pair, the 128-bit
+//! composite reduce, and one spelling per group (the word's first
+//! occurrence, sliced out of `text`). No decode map: identity is the
+//! table's 128 bits end to end. Single rank, text.size() < 4 GiB. Returns a
+//! host DIA, as ReduceByKey does; output order is arbitrary.
+inline DIA<std::pair<std::string, size_t> >
+TextWordCount(Context& ctx, const std::string& text) {
+    using Pair = std::pair<std::string, size_t>;
+    std::vector<Pair> out;
+    const uint64_t nbytes = text.size();
+    if (nbytes >= (1ull << 32))
+        throw std::runtime_error("TextWordCount: input of 4 GiB or more");
+    if (nbytes == 0) return FromVector(ctx, out);
+    hipStream_t s = ctx.stream();
+    t9_context* nat = ctx.native();
+
+    DeviceBuf dtext(nbytes);
+    T9_DIA_HIP(hipMemcpyAsync(dtext.ptr, text.data(), nbytes,
+                              hipMemcpyHostToDevice, s));
+    const uint64_t tok_cap = (nbytes + 1) / 2;
+    DeviceBuf doff(tok_cap * 4), dlen(tok_cap * 4), dn(8), derr(4);
+    DeviceBuf ws(t9_text_tokenize_workspace(nbytes));
+    T9_DIA_TRY(t9_text_tokenize(nat, (const uint8_t*)dtext.ptr, nbytes,
+                                (uint32_t*)doff.ptr, (uint32_t*)dlen.ptr,
+                                (uint64_t*)dn.ptr, ws.ptr, s));
+    uint64_t ntok = 0;
+    T9_DIA_HIP(hipMemcpyAsync(&ntok, dn.ptr, 8, hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipStreamSynchronize(s));
+    if (ntok == 0) return FromVector(ctx, out);
+
+    DeviceBuf d1(ntok * 8), d2(ntok * 8);
+    T9_DIA_TRY(t9_text_hash2(nat, (const uint8_t*)dtext.ptr, nbytes,
+                             (const uint32_t*)doff.ptr,
+                             (const uint32_t*)dlen.ptr, ntok,
+                             (uint64_t*)d1.ptr, (uint64_t*)d2.ptr,
+                             (uint32_t*)derr.ptr, s));
+    uint32_t herr = 0;
+    T9_DIA_HIP(hipMemcpyAsync(&herr, derr.ptr, 4, hipMemcpyDeviceToHost, s));
+
+    uint64_t cap = 1024;
+    while (cap < 2 * ntok + 2) cap <<= 1;
+    DeviceBuf tbl(3 * cap * 8), o1(cap * 8), o2(cap * 8), ov(cap * 8);
+    T9_DIA_TRY(t9_reduce128_init(nat, (uint64_t*)tbl.ptr, cap, s));
+    T9_DIA_TRY(t9_reduce128_build(nat, (const uint64_t*)d1.ptr,
+                                  (const uint64_t*)d2.ptr, nullptr, ntok,
+                                  (uint64_t*)tbl.ptr, cap, 0,
+                                  (uint32_t*)derr.ptr, s));
+    T9_DIA_TRY(t9_reduce128_drain(nat, (const uint64_t*)tbl.ptr, cap,
+                                  (uint64_t*)o1.ptr, (uint64_t*)o2.ptr,
+                                  (uint64_t*)ov.ptr, (uint64_t*)dn.ptr, s));
+    uint64_t m = 0;
+    uint32_t err = 0;
+    T9_DIA_HIP(hipMemcpyAsync(&m, dn.ptr, 8, hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipMemcpyAsync(&err, derr.ptr, 4, hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipStreamSynchronize(s));
+    if (herr) throw std::runtime_error("TextWordCount: bad token range");
+    if (err) throw std::runtime_error("TextWordCount: table overflow");
+    if (m == 0) return FromVector(ctx, out);
+
+    // slot of every token -> first token per slot -> the drained groups'
+    // slots pick their representative; 4-byte records gathered by the
+    // u32 slot / token number
+    DeviceBuf dslot(ntok * 4), dfirst(cap * 4), dgslot(m * 4);
+    DeviceBuf drep(m * 4), droff(m * 4), drlen(m * 4);
+    T9_DIA_TRY(t9_reduce128_lookup(nat, (const uint64_t*)d1.ptr,
+                                   (const uint64_t*)d2.ptr, ntok,
+                                   (const uint64_t*)tbl.ptr, cap, 0,
+                                   (uint32_t*)dslot.ptr, s));
+    T9_DIA_TRY(t9_text_first_token(nat, (const uint32_t*)dslot.ptr, ntok,
+                                   (uint32_t*)dfirst.ptr, cap, s));
+    T9_DIA_TRY(t9_reduce128_lookup(nat, (const uint64_t*)o1.ptr,
+                                   (const uint64_t*)o2.ptr, m,
+                                   (const uint64_t*)tbl.ptr, cap, 0,
+                                   (uint32_t*)dgslot.ptr, s));
+    // every drained key is in the table, so its slot is a valid index
+    // (checked on the host below before the dependent gathers' results
+    // are used; an absent slot would index past dfirst)
+    std::vector<uint32_t> gslot(m);
+    T9_DIA_HIP(hipMemcpyAsync(gslot.data(), dgslot.ptr, m * 4,
+                              hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < m; ++i)
+        if (gslot[i] >= cap)
+            throw std::runtime_error("TextWordCount: drained key not found");
+    T9_DIA_TRY(t9_gather_records(nat, (const uint8_t*)dfirst.ptr,
+                                 (const uint32_t*)dgslot.ptr, m, 4,
+                                 (uint8_t*)drep.ptr, s));
+    std::vector<uint32_t> rep(m);
+    T9_DIA_HIP(hipMemcpyAsync(rep.data(), drep.ptr, m * 4,
+                              hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < m; ++i)
+        if (rep[i] >= ntok)
+            throw std::runtime_error("TextWordCount: group without a token");
+    T9_DIA_TRY(t9_gather_records(nat, (const uint8_t*)doff.ptr,
+                                 (const uint32_t*)drep.ptr, m, 4,
+                                 (uint8_t*)droff.ptr, s));
+    T9_DIA_TRY(t9_gather_records(nat, (const uint8_t*)dlen.ptr,
+                                 (const uint32_t*)drep.ptr, m, 4,
+                                 (uint8_t*)drlen.ptr, s));
+    std::vector<uint32_t> roff(m), rlen(m);
+    std::vector<uint64_t> rv(m);
+    T9_DIA_HIP(hipMemcpyAsync(roff.data(), droff.ptr, m * 4,
+                              hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipMemcpyAsync(rlen.data(), drlen.ptr, m * 4,
+                              hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipMemcpyAsync(rv.data(), ov.ptr, m * 8,
+                              hipMemcpyDeviceToHost, s));
+    T9_DIA_HIP(hipStreamSynchronize(s));
+    out.reserve(m);
+    for (uint64_t i = 0; i < m; ++i)
+        out.emplace_back(text.substr(roff[i], rlen[i]), (size_t)rv[i]);
+    return FromVector(ctx, out);
 }
 
 //! ReadBinary — reference api/read_binary.hpp: read packed fixed-size

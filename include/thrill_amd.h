@@ -245,6 +245,16 @@ int t9_reduce128_drain(t9_context* ctx, const uint64_t* d_table,
                        uint64_t capacity, uint64_t* d_out_k1,
                        uint64_t* d_out_k2, uint64_t* d_out_vals,
                        uint64_t* d_out_n, void* stream);
+/* Read-only probe of a built 128-bit table: d_slot[i] = slot index holding
+ * (k1[i], k2[i]), or 0xFFFFFFFF if absent. capacity <= 2^31. Same start
+ * slot, probe order and slot stride as build/init/drain; at most
+ * `capacity` probes per key, so a full table terminates. Slot indices give
+ * every reduced group a dense-enough integer name (< capacity) without a
+ * host-side decode map. */
+int t9_reduce128_lookup(t9_context* ctx, const uint64_t* d_k1,
+                        const uint64_t* d_k2, uint64_t n,
+                        const uint64_t* d_table, uint64_t capacity,
+                        uint64_t salt, uint32_t* d_slot, void* stream);
 /* two independent 64-bit hashes of u64 token ids (synthetic stand-in for
  * hashing the word bytes at tokenize time; remaps the reserved
  * sentinels) */
@@ -256,6 +266,51 @@ int t9_hash2_of(t9_context* ctx, const uint64_t* d_ids, uint64_t n,
 int t9_bucket_mod(t9_context* ctx, const uint64_t* d_keys, uint64_t n,
                   uint32_t p, uint32_t* d_bucket, uint64_t* d_counts,
                   void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Real text — the word_count PreOp on the device. ReadLines splits at
+ * '\n' (thrill/api/read_lines.hpp) and WordCount splits lines at ' ',
+ * dropping empty words (examples/word_count/word_count.hpp:37-45): a
+ * token is a maximal run of bytes that are neither 0x20 nor 0x0A. Every
+ * other byte value (0x00, '\t', '\r', 0x80-0xFF) is a word byte, and a
+ * token running to the end of the buffer is a token. Together with
+ * t9_reduce128_* and t9_reduce128_lookup these give (word, count) pairs
+ * from raw bytes with 128-bit identity end to end (DESIGN.md "Real text:
+ * device tokenizer and hasher").
+ * ------------------------------------------------------------------ */
+
+/* Workspace bytes for t9_text_tokenize; pure host code. */
+uint64_t t9_text_tokenize_workspace(uint64_t nbytes);
+/* Tokens of d_text[0..nbytes) in text order. d_text 16-byte aligned,
+ * nbytes < 2^32 (T9_EINVAL otherwise). d_tok_off[i] = byte offset of
+ * token i, d_tok_len[i] = its length (>= 1), *d_ntok (device u64, zeroed
+ * by the call) = count. d_tok_off == NULL && d_tok_len == NULL: count
+ * only. Output capacity (nbytes+1)/2 always suffices. Never touches a
+ * byte outside [d_text, d_text+nbytes). */
+int t9_text_tokenize(t9_context* ctx, const uint8_t* d_text,
+                     uint64_t nbytes, uint32_t* d_tok_off,
+                     uint32_t* d_tok_len, uint64_t* d_ntok,
+                     void* d_workspace, void* stream);
+
+/* (k1, k2) of n byte ranges of d_text (8-byte aligned): FNV-1a over the
+ * unsigned bytes under two bases, each mixed by Hash128to64, reserved
+ * sentinels remapped — bit-equal to detail::string_hash2 of t9/dia.hpp.
+ * len 0 is legal (hash of the empty string). Never reads outside
+ * [d_text, d_text+nbytes); off+len > nbytes for any i is a caller error
+ * reported through d_error (device u32, zeroed by the call), not a read
+ * (that entry's k1/k2 are written as 0). */
+int t9_text_hash2(t9_context* ctx, const uint8_t* d_text, uint64_t nbytes,
+                  const uint32_t* d_off, const uint32_t* d_len, uint64_t n,
+                  uint64_t* d_k1, uint64_t* d_k2, uint32_t* d_error,
+                  void* stream);
+
+/* d_first[s] = min{ i : d_slot[i] == s }, 0xFFFFFFFF for untouched slots;
+ * d_first has `capacity` entries and is initialised by the call.
+ * n < 2^32. Entries of d_slot equal to 0xFFFFFFFF (or >= capacity) are
+ * skipped. With d_slot from t9_reduce128_lookup over all tokens this
+ * names each group's first occurrence — the spelling to report. */
+int t9_text_first_token(t9_context* ctx, const uint32_t* d_slot, uint64_t n,
+                        uint32_t* d_first, uint64_t capacity, void* stream);
 
 /* ReduceToIndex — reference
  * api/reduce_to_index.hpp + core/reduce_by_index_post_phase.hpp with the

@@ -358,6 +358,30 @@ __device__ inline void t9_g128_insert(u64* __restrict__ tb, u64 cap,
     }
 }
 
+/* read-only probe of a built table: same start slot, probe order and slot
+ * stride as t9_g128_insert. Stops at a slot whose k1 is empty (an insert
+ * would have claimed it) and after cap probes (a full table terminates). */
+__global__ __launch_bounds__(256) void k_reduce128_lookup(
+    const u64* __restrict__ k1s, const u64* __restrict__ k2s, u64 n,
+    const u64* __restrict__ tb, u64 cap, u64 salt, u32 sstr,
+    u32* __restrict__ out) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u64 k1 = k1s[i], k2 = k2s[i];
+    u64 slot = t9_hash128to64(salt, k1) & (cap - 1);
+    u32 found = 0xFFFFFFFFu;
+    for (u64 probes = 0; probes < cap; ++probes) {
+        const u64 p1 = tb[sstr * slot];
+        if (p1 == T9_EMPTY) break;
+        if (p1 == k1 && tb[sstr * slot + 1] == k2) {
+            found = (u32)slot;
+            break;
+        }
+        slot = (slot + 1) & (cap - 1);
+    }
+    out[i] = found;
+}
+
 /* LDS-accumulated 128-bit build: per-block (k1, k2, sum) filter table
  * absorbing the Zipf head at LDS-atomic speed (same design as
  * k_reduce_build_lds, composite equality). SLOTS x 24 B of LDS. */
@@ -858,6 +882,23 @@ int t9_reduce128_drain(t9_context* ctx, const u64* d_table, u64 cap,
     hipLaunchKernelGGL(k_reduce128_drain, dim3(grid_for(cap)), dim3(256),
                        0, s, d_table, cap, d_ok1, d_ok2, d_ov, d_out_n,
                        r128_stride());
+    T9_LAUNCH_CHECK();
+    return T9_OK;
+}
+
+int t9_reduce128_lookup(t9_context* ctx, const u64* d_k1, const u64* d_k2,
+                        u64 n, const u64* d_table, u64 cap, u64 salt,
+                        u32* d_slot, void* stream) {
+    (void)ctx;
+    /* slot indices are u32 with 0xFFFFFFFF reserved for "absent" */
+    if (!d_table || !is_pow2(cap) || cap > (1ull << 31)) return T9_EINVAL;
+    if (n == 0) return T9_OK;
+    if (!d_k1 || !d_k2 || !d_slot) return T9_EINVAL;
+    const u64 blocks = t9_ceil_div(n, 256);
+    if (blocks >= (1ull << 31)) return T9_EINVAL;
+    hipLaunchKernelGGL(k_reduce128_lookup, dim3((u32)blocks), dim3(256), 0,
+                       (hipStream_t)stream, d_k1, d_k2, n, d_table, cap,
+                       salt, r128_stride(), d_slot);
     T9_LAUNCH_CHECK();
     return T9_OK;
 }

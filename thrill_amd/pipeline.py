@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from .native import Native
+from .native import Native, T9Error
 
 REC = 100  # TeraSort record bytes (examples/terasort/terasort.cpp:31-43)
 
@@ -476,6 +476,94 @@ class TeraSort:
         nat.sort_records(_ptr(d_recv), _ptr(d_sorted), n_recv, REC, 10,
                          _ptr(ws), s)
         return d_sorted, n_recv
+
+    def close(self):
+        self.nat.close()
+
+
+class TextWordCount:
+    """word_count over raw text bytes, single rank: tokenize -> hash ->
+    128-bit reduce -> one spelling per group, all on the device
+    (t9_text_* / t9_reduce128_*; DESIGN.md "Real text: device tokenizer
+    and hasher"). A token is a maximal run of bytes other than ' ' and
+    '\\n' — the reference's ReadLines + WordCount split. There is no
+    decode map: a group's word is sliced out of the input at its first
+    occurrence, so identity is the table's 128 bits end to end."""
+
+    def __init__(self, device=0):
+        self.nat = Native(device=device)
+
+    def count(self, data, capacity=None):
+        """{word bytes: occurrences} of `data` (bytes, < 4 GiB)."""
+        offs, lens, cnts = self.groups(data, capacity)
+        return {data[int(o):int(o) + int(l)]: int(c)
+                for o, l, c in zip(offs, lens, cnts)}
+
+    def groups(self, data, capacity=None):
+        """One (offset, length, count) triple per distinct word, as three
+        numpy arrays in arbitrary group order: data[offset:offset+length]
+        is the word's FIRST occurrence in `data`."""
+        nat, s = self.nat, _stream()
+        nbytes = len(data)
+        i32, i64 = torch.int32, torch.int64
+        d_text = torch.from_numpy(
+            np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+        tok_cap = max((nbytes + 1) // 2, 1)
+        d_off = torch.empty(tok_cap, dtype=i32, device="cuda")
+        d_len = torch.empty(tok_cap, dtype=i32, device="cuda")
+        d_n = torch.empty(1, dtype=i64, device="cuda")
+        d_err = torch.empty(1, dtype=i32, device="cuda")
+        d_ws = torch.empty(int(nat.ws("text_tokenize", nbytes)),
+                           dtype=torch.uint8, device="cuda")
+        nat.text_tokenize(_ptr(d_text), nbytes, _ptr(d_off), _ptr(d_len),
+                          _ptr(d_n), _ptr(d_ws), s)
+        ntok = int(d_n.cpu().item())
+        if ntok == 0:
+            return (np.zeros(0, np.uint32), np.zeros(0, np.uint32),
+                    np.zeros(0, np.uint64))
+        d_k1 = torch.empty(ntok, dtype=i64, device="cuda")
+        d_k2 = torch.empty(ntok, dtype=i64, device="cuda")
+        nat.text_hash2(_ptr(d_text), nbytes, _ptr(d_off), _ptr(d_len), ntok,
+                       _ptr(d_k1), _ptr(d_k2), _ptr(d_err), s)
+        if int(d_err.cpu().item()):
+            raise T9Error("text_hash2: token range outside the text")
+
+        if capacity is None:
+            capacity = 1 << max(10, (2 * ntok + 1).bit_length())
+        cap = int(capacity)
+        d_tbl = torch.empty(3 * cap, dtype=i64, device="cuda")
+        d_o1 = torch.empty(cap, dtype=i64, device="cuda")
+        d_o2 = torch.empty(cap, dtype=i64, device="cuda")
+        d_ov = torch.empty(cap, dtype=i64, device="cuda")
+        nat.reduce128_init(_ptr(d_tbl), cap, s)
+        nat.reduce128_build(_ptr(d_k1), _ptr(d_k2), None, ntok, _ptr(d_tbl),
+                            cap, 0, _ptr(d_err), s)
+        if int(d_err.cpu().item()):
+            raise T9Error(f"TextWordCount: table overflow (capacity {cap})")
+        nat.reduce128_drain(_ptr(d_tbl), cap, _ptr(d_o1), _ptr(d_o2),
+                            _ptr(d_ov), _ptr(d_n), s)
+        m = int(d_n.cpu().item())
+
+        # each group's first token: slot of every token -> min token index
+        # per slot -> read at the drained keys' slots
+        d_slot = torch.empty(ntok, dtype=i32, device="cuda")
+        d_first = torch.empty(cap, dtype=i32, device="cuda")
+        d_gslot = torch.empty(m, dtype=i32, device="cuda")
+        nat.reduce128_lookup(_ptr(d_k1), _ptr(d_k2), ntok, _ptr(d_tbl), cap,
+                             0, _ptr(d_slot), s)
+        nat.text_first_token(_ptr(d_slot), ntok, _ptr(d_first), cap, s)
+        nat.reduce128_lookup(_ptr(d_o1), _ptr(d_o2), m, _ptr(d_tbl), cap, 0,
+                             _ptr(d_gslot), s)
+        if int((d_gslot < 0).any().item()):
+            raise T9Error("TextWordCount: drained key not found in table")
+        rep = d_first[d_gslot.long()]
+        if int((rep < 0).any().item()):
+            raise T9Error("TextWordCount: group without a first token")
+        rep = rep.long()
+        offs = d_off[rep].cpu().numpy().view(np.uint32)
+        lens = d_len[rep].cpu().numpy().view(np.uint32)
+        cnts = d_ov[:m].cpu().numpy().view(np.uint64)
+        return offs, lens, cnts
 
     def close(self):
         self.nat.close()
