@@ -130,6 +130,14 @@ int t9_sort_records_keyle(t9_context* ctx, const uint8_t* d_in,
  * is unchanged. A context is driven by ONE host thread at a time. */
 int t9_sort_last_schedule(const t9_context* ctx);
 
+/* How the last t9_sort_records / t9_sort_records_keyle call on this context
+ * counted keys equal to their neighbour (the probe that decides whether the
+ * tie machinery runs): 1 = the sub-bucket sort counted them while it held
+ * each sub-bucket sorted (the default two-level flow with every sub-bucket
+ * within the single-wave sort's limit); 0 = a standalone pass over the
+ * sorted keys (every other flow). The sorted output is the same. */
+int t9_sort_last_tiecount(const t9_context* ctx);
+
 /* ------------------------------------------------------------------ *
  * Classification + partition — replaces TransmitItems' tree-descent loop
  * (thrill/api/sort.hpp:434-535). bucket(item i) = #{ j : (splitter_key[j],

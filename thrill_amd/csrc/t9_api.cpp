@@ -35,6 +35,7 @@ int t9_create(t9_context** out, int device, int rank, int world,
     for (int i = 0; i <= T9_OVERLAP_MAXK; ++i) ctx->ov_ev[i] = nullptr;
     ctx->ov_ready = 0;
     ctx->last_schedule = 0;
+    ctx->last_tiecount = 0;
     *out = ctx;
     return T9_OK;
 }
@@ -76,6 +77,10 @@ int t9i_overlap_init(t9_context* ctx) {
 
 int t9_sort_last_schedule(const t9_context* ctx) {
     return ctx ? ctx->last_schedule : T9_EINVAL;
+}
+
+int t9_sort_last_tiecount(const t9_context* ctx) {
+    return ctx ? ctx->last_tiecount : T9_EINVAL;
 }
 
 /* ------------------------------------------------------------------ *

@@ -158,20 +158,80 @@ __global__ __launch_bounds__(BLOCK, 2) void k_bitonic_sort_sub(
  * per lane. The in-lane sort is a pure-VALU bitonic network over
  * registers (zero LDS traffic where the radix sort spends 4 of its 6
  * passes), then 6 merge rounds (16->1024) via merge-path splits into
- * LDS: ~2 LDS writes + ~3 LDS reads per element per round. With a
- * 64-thread block every __syncthreads() compiles to a wave-level
+ * LDS: one 16-byte-slot row store per lane, the binary search, and one
+ * LDS read per merged element (the two run heads stay in registers).
+ * With a 64-thread block every __syncthreads() compiles to a wave-level
  * scheduling barrier (no s_barrier cost). Same stable-composite scheme
  * as k_bitonic_sort_sub above.
+ *
+ * k_wave16_sort_sub moves its global data through the same LDS buffer:
+ * lane t loads and stores positions t + BLOCK * r (contiguous across the
+ * wave) and the buffer turns them into 16 contiguous elements per lane
+ * and back. Measured at the 10 GiB record sort:
+ * 2.37 ms with lane-strided global I/O and a linear LDS image, 0.93 ms
+ * now; the swizzle and the single-read merge only pay once the global
+ * I/O is coalesced (before that they measured +0.18 ms).
  * ------------------------------------------------------------------ */
-template <int NSORT, int BLOCK, bool HAS_VAL>
+typedef unsigned long long t9_u64x2 __attribute__((ext_vector_type(2)));
+
+/* LDS image of the composites: element e lives at lc[t9_w16_phys(e)].
+ * Lane-row l = e >> 4 is 8 slots of 16 bytes; slot k of row l is stored at
+ * slot k ^ (l & 7) of the same row (no padding, NSORT * 8 bytes). A lane's
+ * eight 16-byte row accesses then fall on eight different bank quads within
+ * every group of 8 lanes, and the merge's reads, whose lanes sit about 8
+ * elements apart, spread over 16 bank pairs instead of 4. The swizzle never
+ * splits a 16-byte slot, so a row moves as eight 128-bit accesses. */
+__device__ __forceinline__ u32 t9_w16_phys(u32 e) {
+    return e ^ (((e >> 4) & 7u) << 1);
+}
+
+/* lane `row` <-> its 16 contiguous elements, as 8 swizzled 16-byte slots */
+__device__ __forceinline__ void t9_w16_row_store(u64* lc, u32 row,
+                                                 const u64 (&c)[16]) {
+    /* row * 16 + ((k ^ x) << 1) == (row * 16 + (x << 1)) ^ (k << 1) */
+    const u32 base = row * 16 + ((row & 7u) << 1);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        t9_u64x2 v2;
+        v2.x = c[2 * k];
+        v2.y = c[2 * k + 1];
+        *(t9_u64x2*)&lc[base ^ ((u32)k << 1)] = v2;
+    }
+}
+
+__device__ __forceinline__ void t9_w16_row_load(const u64* lc, u32 row,
+                                                u64 (&c)[16]) {
+    const u32 base = row * 16 + ((row & 7u) << 1);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const t9_u64x2 v2 = *(const t9_u64x2*)&lc[base ^ ((u32)k << 1)];
+        c[2 * k] = v2.x;
+        c[2 * k + 1] = v2.y;
+    }
+}
+
+/* REC (record sort only; needs HAS_VAL): the block also counts its
+ * equal-key neighbours into *ntied — the number k_count_tied would find in
+ * this sub-bucket; ties cannot cross sub-buckets, whose top key bits
+ * differ — and writes its sorted KEYS back only if it found one.
+ * Invariant the record sort relies on: a sub-bucket whose keys were not
+ * written still holds its own keys, all distinct, in unsorted order, so no
+ * two neighbours in it are equal (k_tie_flags flags nothing there) and
+ * every later reader of the key array touches tied positions only, which
+ * lie in written sub-buckets. The values are always written. The public
+ * pair and key sorts instantiate REC = false and get fully sorted keys. */
+template <int NSORT, int BLOCK, bool HAS_VAL, bool REC>
 __global__ __launch_bounds__(BLOCK, 2) void k_wave16_sort_sub(
     u64* __restrict__ keys, u32* __restrict__ vals,
-    const u32* __restrict__ sub_start, const u32* __restrict__ sub_n) {
+    const u32* __restrict__ sub_start, const u32* __restrict__ sub_n,
+    u32* __restrict__ ntied) {
     constexpr int E = NSORT / BLOCK;
     static_assert(E == 16, "wave16 mapping: 16 elements per lane");
+    static_assert(HAS_VAL || !REC, "the tie count rides the pair sort");
     constexpr int ROUNDS = (NSORT == 1024) ? 6 : (NSORT == 2048) ? 7 : 8;
-    __shared__ u64 lc[NSORT];
+    __shared__ __attribute__((aligned(16))) u64 lc[NSORT];
     __shared__ u32 s_differ;
+    __shared__ u32 s_ntie;
 
     const u32 sb = blockIdx.x;
     const u32 ns = sub_n[sb];
@@ -180,7 +240,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_wave16_sort_sub(
     const u32 lane = threadIdx.x;   /* block-level thread id */
     const u32 e0 = lane * E;
 
-    if (lane == 0) s_differ = 0;
+    if (lane == 0) { s_differ = 0; s_ntie = 0; }
     __syncthreads();
 
     const u64 mask48 = 0x0000FFFFFFFFFFFFull;
@@ -194,20 +254,31 @@ __global__ __launch_bounds__(BLOCK, 2) void k_wave16_sort_sub(
      * limiter of this barrier-parked kernel) */
     u64 c[E];
     u32 differ = 0;
+    /* block-uniform bases: the per-lane part of every global address is a
+     * 32-bit offset below NSORT elements */
+    u64* const kb = keys + gbase;
+    u32* const vb = HAS_VAL ? vals + gbase : nullptr;
+    /* coalesced load (lane t takes positions t + BLOCK * r), staged
+     * through lc so that each lane then owns 16 contiguous elements */
 #pragma unroll
     for (int r = 0; r < E; ++r) {
-        const u32 i = e0 + r;
-        if (i < ns) {
-            const u64 k = keys[gbase + i];
-            c[r] = ((k & mask48) << 12) | (u64)i;
+        const u32 p = lane + (u32)BLOCK * r;
+        u64 cc = ~0ull;
+        if (p < ns) {
+            const u64 k = kb[p];
+            cc = ((k & mask48) << 12) | (u64)p;
             differ |= ((k & mask48) != ref48);
-        } else {
-            c[r] = ~0ull;
         }
+        lc[t9_w16_phys(p)] = cc;
     }
     if (differ) s_differ = 1;
     __syncthreads();
-    if (!s_differ) return;
+    if (!s_differ) {
+        /* all keys equal: in stable order as they lie, ns - 1 ties */
+        if (REC && lane == 0) atomicAdd(ntied, ns - 1);
+        return;
+    }
+    t9_w16_row_load(lc, lane, c);
 
     /* in-register bitonic sort of the lane's 16 elements (pure VALU) */
 #pragma unroll
@@ -236,47 +307,94 @@ __global__ __launch_bounds__(BLOCK, 2) void k_wave16_sort_sub(
     for (int lm = 0; lm < ROUNDS; ++lm) {
         const u32 L = (u32)E << lm;
         __syncthreads();
-#pragma unroll
-        for (int r = 0; r < E; ++r) lc[e0 + r] = c[r];
+        t9_w16_row_store(lc, lane, c);
         __syncthreads();
         const u32 pairbase = e0 & ~(2 * L - 1);
         const u32 d = e0 - pairbase;          /* my first output diagonal */
-        const u64* A = lc + pairbase;
-        const u64* B = lc + pairbase + L;
+        const u32 ab = pairbase, bb = pairbase + L;   /* run A, run B */
         u32 lo = (d > L) ? d - L : 0;
         u32 hi = (d < L) ? d : L;
         while (lo < hi) {
             const u32 m = (lo + hi) >> 1;
-            if (A[m] <= B[d - m - 1]) lo = m + 1;
+            if (lc[t9_w16_phys(ab + m)] <= lc[t9_w16_phys(bb + d - m - 1)])
+                lo = m + 1;
             else hi = m;
         }
-        u32 i = lo, j = d - lo;
+        /* both run heads live in registers; each step emits the
+         * smaller one and reads only that side's successor. An
+         * exhausted run reads as ~0, above every live composite
+         * (60 bits) and equal to the pads, which never leave. */
+        u32 ia = ab + lo, ib = bb + (d - lo);
+        const u32 ea = bb, eb = bb + L;
+        /* reads are unconditional at a clamped index and the value is
+         * selected afterwards: no divergent branch per step */
+        const u64 a0 = lc[t9_w16_phys(ia < ea ? ia : ab)];
+        const u64 b0 = lc[t9_w16_phys(ib < eb ? ib : ab)];
+        u64 a = (ia < ea) ? a0 : ~0ull;
+        u64 b = (ib < eb) ? b0 : ~0ull;
 #pragma unroll
         for (int r = 0; r < E; ++r) {
-            const bool ta = (j >= L) || (i < L && A[i] <= B[j]);
-            c[r] = (ta ? A[i] : B[j]);
-            if (ta) ++i; else ++j;
+            const bool ta = a <= b;
+            c[r] = ta ? a : b;
+            if (r + 1 < E) {
+                ia += ta ? 1u : 0u;
+                ib += ta ? 0u : 1u;
+                const u32 nx = ta ? ia : ib;
+                const bool in = nx < (ta ? ea : eb);
+                const u64 ld = lc[t9_w16_phys(in ? nx : ab)];
+                const u64 nv = in ? ld : ~0ull;
+                a = ta ? nv : a;
+                b = ta ? b : nv;
+            }
         }
     }
 
-    /* writeback: keys from the composite; values re-gathered from their
-     * embedded original positions. All reads complete before any lane
-     * writes (barrier), since the sort is in place. */
+    /* the sorted composites go back into lc so that the write-back is
+     * contiguous: lane t handles output positions p = t + BLOCK * r */
+    __syncthreads();
+    t9_w16_row_store(lc, lane, c);
+    __syncthreads();
+    if (REC) {
+        /* ties among my 16 sorted elements and against the next lane's
+         * first; a pad (~0) equals no live element, and pad pairs are
+         * excluded by the bound */
+        const u64 nxt = (e0 + E < (u32)NSORT) ? lc[t9_w16_phys(e0 + E)]
+                                              : ~0ull;
+        u32 cnt = 0;
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+            const u64 hi = (r + 1 < E) ? c[r + 1] : nxt;
+            cnt += (e0 + r + 1 < ns) && ((c[r] >> 12) == (hi >> 12));
+        }
+        if (cnt) atomicAdd(&s_ntie, cnt);
+    }
+    /* values re-gathered from the embedded original positions. All reads
+     * complete before any lane writes (barrier), since the sort is in
+     * place. */
     u32 v[HAS_VAL ? E : 1];
     if (HAS_VAL) {
 #pragma unroll
         for (int r = 0; r < E; ++r) {
-            const u32 i = e0 + r;
-            if (i < ns) v[r] = vals[gbase + (u32)(c[r] & 0xFFFu)];
+            const u32 p = lane + (u32)BLOCK * r;
+            if (p < ns) v[r] = vb[(u32)lc[t9_w16_phys(p)] & 0xFFFu];
         }
     }
     __syncthreads();
+    const u32 nt = REC ? s_ntie : 0u;
+    if (REC && lane == 0 && nt) atomicAdd(ntied, nt);
+    if (HAS_VAL) {
 #pragma unroll
-    for (int r = 0; r < E; ++r) {
-        const u32 i = e0 + r;
-        if (i < ns) {
-            keys[gbase + i] = high16 | (c[r] >> 12);
-            if (HAS_VAL) vals[gbase + i] = v[r];
+        for (int r = 0; r < E; ++r) {
+            const u32 p = lane + (u32)BLOCK * r;
+            if (p < ns) vb[p] = v[r];
+        }
+    }
+    /* lc still holds the sorted composites (nothing wrote it since) */
+    if (!REC || nt) {
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+            const u32 p = lane + (u32)BLOCK * r;
+            if (p < ns) kb[p] = high16 | (lc[t9_w16_phys(p)] >> 12);
         }
     }
 }

@@ -56,19 +56,19 @@ struct t9_context {
     hipEvent_t ov_ev[T9_OVERLAP_MAXK + 1];
     int ov_ready;
     int last_schedule;   /* t9_sort_last_schedule */
+    int last_tiecount;   /* t9_sort_last_tiecount */
 };
 
 /* record-sort request riding along the pair sort: when the two-level
  * 9-bit MSB flow can, it gathers out[a..b) = recs[idx[a..b)] chunk by
  * chunk on the context's internal stream while later sub-buckets are
- * still being sorted, and counts equal-prefix neighbours into d_ntied
- * (zeroed by the sort). chunks stays 0 when the serial schedule ran —
- * then the caller counts ties and gathers itself. */
+ * still being sorted; the sub-sort's own tie counter (the d_ntied passed
+ * next to this request) is the gathers' abort flag. chunks stays 0 when
+ * the serial schedule ran — then the caller gathers itself. */
 struct t9_overlap_req {
     const u8* recs;
     u8* out;
     u32 rec_words;
-    u32* d_ntied;
     u32 chunks;   /* out: non-empty chunks gathered on the internal stream */
 };
 

@@ -25,7 +25,8 @@ extern "C" u64 t9_partition_idx_workspace(u64 n);
 extern "C" int t9_partition_idx(t9_context*, const u32*, u64, u32, u32*,
                                 u64*, void*, void*);
 extern "C" int t9i_sort_pairs_msb_ph(t9_context*, u64*, u32*, u64, void*,
-                                     void*, int, t9_overlap_req*);
+                                     void*, int, t9_overlap_req*, u32*,
+                                     int*);
 extern "C" u32* t9i_msb_pass1_hist(void* d_workspace, u64 n);
 
 /* ------------------------------------------------------------------ */
@@ -853,8 +854,14 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
     bool fused = fe && atoi(fe) && n >= (1ull << 14) &&
                  (rec_size == 100 || rec_size == 128);
     int rc;
-    t9_overlap_req ov = { nullptr, nullptr, 0, nullptr, 0 };
-    if (ctx) ctx->last_schedule = 0;
+    t9_overlap_req ov = { nullptr, nullptr, 0, 0 };
+    /* 1: the sub-bucket sort counted the ties into d_ntied itself; then
+     * d_keys is sorted only inside sub-buckets that hold a tie (see
+     * k_wave16_sort_sub), which is all its readers below need: k_tie_flags
+     * compares neighbours (none equal in an unwritten sub-bucket, whose
+     * keys are distinct) and the tied-prefix gather reads tied positions */
+    int tie_counted = 0;
+    if (ctx) { ctx->last_schedule = 0; ctx->last_tiecount = 0; }
     if (eh && !fused) {
         u32* hist = t9i_msb_pass1_hist(pair_ws, n);
         const u64 B = t9_ceil_div(n, 8192);
@@ -885,10 +892,10 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
             ov.recs = d_in;
             ov.out = d_out;
             ov.rec_words = rw;
-            ov.d_ntied = d_ntied;
         }
         rc = t9i_sort_pairs_msb_ph(ctx, d_keys, d_idx, n, pair_ws, stream,
-                                   widx ? 0 : 1, may_overlap ? &ov : nullptr);
+                                   widx ? 0 : 1, may_overlap ? &ov : nullptr,
+                                   d_ntied, &tie_counted);
     }
     else if (fused && !le) {
         rc = t9i_sort_recs_msb(ctx, d_in, rec_size, d_keys, d_idx, n,
@@ -903,12 +910,15 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
         rc = t9_sort_pairs_u64_u32(ctx, d_keys, d_idx, n, pair_ws, stream);
     }
     if (rc) return rc;
-    /* overlapped schedule: ties are already counted chunk by chunk and
-     * the caller's stream has joined the internal one */
-    if (!ov.chunks) {
+    /* standalone count only where the sub-bucket sort did not count
+     * (oversize sub-buckets, a sub-sort other than wave16, the 8-bit,
+     * 3-level and LSD flows). Overlapped schedule: the caller's stream has
+     * joined the internal one. */
+    if (!tie_counted) {
         rc = t9i_count_tied(d_keys, n, d_ntied, s);
         if (rc) return rc;
     }
+    if (ctx) ctx->last_tiecount = tie_counted;
     u32 ntied = 0;
     HIP_TRY(hipMemcpyAsync(&ntied, d_ntied, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

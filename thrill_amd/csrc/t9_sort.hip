@@ -834,17 +834,4 @@ int t9i_count_tied(const u64* d_keys, u64 n, u32* d_ntied, hipStream_t s) {
     return T9_OK;
 }
 
-/* internal: the same count over one chunk of the keys, ADDED to *d_ntied
- * (the chunked sort -> gather pipeline zeroes it once, before chunk 0) */
-int t9i_count_tied_acc(const u64* d_keys, u64 n, u32* d_ntied,
-                       hipStream_t s) {
-    if (n < 2) return T9_OK;
-    u64 want = t9_ceil_div(n, 256);
-    u32 grid = (u32)((want < 2048) ? want : 2048);
-    hipLaunchKernelGGL(k_count_tied, dim3(grid), dim3(256), 0, s, d_keys, n,
-                       d_ntied);
-    T9_LAUNCH_CHECK();
-    return T9_OK;
-}
-
 } /* extern "C" */

@@ -648,22 +648,42 @@ static bool t9i_span_wave16() {
     return on;
 }
 
+/* REC: the record-sort form (k_wave16_sort_sub) — ties counted into
+ * d_ntied, keys written back only where a tie was found */
+template <bool HAS_VAL, bool REC>
+static void t9i_launch_wave16_sub_t(u32 grid, u32 maxsub, hipStream_t s,
+                                    u64* d_keys, u32* d_vals,
+                                    const u32* sub_start, const u32* sub_n,
+                                    u32* d_ntied) {
+    if (maxsub <= 1024)
+        hipLaunchKernelGGL((k_wave16_sort_sub<1024, 64, HAS_VAL, REC>),
+                           dim3(grid), dim3(64), 0, s, d_keys, d_vals,
+                           sub_start, sub_n, d_ntied);
+    else if (maxsub <= 2048)
+        hipLaunchKernelGGL((k_wave16_sort_sub<2048, 128, HAS_VAL, REC>),
+                           dim3(grid), dim3(128), 0, s, d_keys, d_vals,
+                           sub_start, sub_n, d_ntied);
+    else
+        hipLaunchKernelGGL((k_wave16_sort_sub<4096, 256, HAS_VAL, REC>),
+                           dim3(grid), dim3(256), 0, s, d_keys, d_vals,
+                           sub_start, sub_n, d_ntied);
+}
+
 template <bool HAS_VAL>
 static void t9i_launch_wave16_sub(u32 grid, u32 maxsub, hipStream_t s,
                                   u64* d_keys, u32* d_vals,
-                                  const u32* sub_start, const u32* sub_n) {
-    if (maxsub <= 1024)
-        hipLaunchKernelGGL((k_wave16_sort_sub<1024, 64, HAS_VAL>),
-                           dim3(grid), dim3(64), 0, s, d_keys, d_vals,
-                           sub_start, sub_n);
-    else if (maxsub <= 2048)
-        hipLaunchKernelGGL((k_wave16_sort_sub<2048, 128, HAS_VAL>),
-                           dim3(grid), dim3(128), 0, s, d_keys, d_vals,
-                           sub_start, sub_n);
-    else
-        hipLaunchKernelGGL((k_wave16_sort_sub<4096, 256, HAS_VAL>),
-                           dim3(grid), dim3(256), 0, s, d_keys, d_vals,
-                           sub_start, sub_n);
+                                  const u32* sub_start, const u32* sub_n,
+                                  u32* d_ntied = nullptr) {
+    if constexpr (HAS_VAL) {
+        if (d_ntied) {
+            t9i_launch_wave16_sub_t<true, true>(grid, maxsub, s, d_keys,
+                                                d_vals, sub_start, sub_n,
+                                                d_ntied);
+            return;
+        }
+    }
+    t9i_launch_wave16_sub_t<HAS_VAL, false>(grid, maxsub, s, d_keys, d_vals,
+                                            sub_start, sub_n, nullptr);
 }
 
 static bool t9i_lds_bitonic() {
@@ -1023,8 +1043,8 @@ extern "C" u64 t9i_sort_pairs_msb_workspace(u64 n) { return msb_ws_bytes(n); }
  * block slots and the LDS pipe and leaves HBM nearly idle; the payload
  * gather is bound by HBM and leaves the LDS pipe idle. The NSUB9
  * sub-buckets are cut into K contiguous ranges: the caller's stream sorts
- * range c, counts its equal-prefix neighbours and records an event; the
- * context's internal stream waits for it and gathers the records of range
+ * range c (the sub-sort counts its equal-prefix neighbours) and records an
+ * event; the context's internal stream waits for it and gathers range
  * c while the caller's stream is already sorting range c + 1. All
  * ordering is by stream events.
  *
@@ -1038,7 +1058,6 @@ extern "C" u64 t9i_sort_pairs_msb_workspace(u64 n) { return msb_ws_bytes(n); }
  * blocks take those slots. DESIGN.md negative-results ledger,
  * profiles/r03_overlap_kernel_trace.txt. */
 extern "C" int t9i_overlap_init(t9_context* ctx);
-extern "C" int t9i_count_tied_acc(const u64*, u64, u32*, hipStream_t);
 extern "C" int t9i_gather_chunk(const u8*, const u32*, u64, u64, u8*,
                                 const u32*, hipStream_t);
 
@@ -1074,7 +1093,9 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                          void* d_workspace, void* stream,
                          bool pre_hist = false,
                          t9_overlap_req* ov = nullptr,
-                         bool iota_vals = false) {
+                         bool iota_vals = false,
+                         u32* d_ntied = nullptr,
+                         int* tie_counted = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     MsbWs w = carve_msb((char*)d_workspace, n);
 
@@ -1157,7 +1178,19 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                                        hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             const u32 maxsub = info[0], novr9 = info[1];
-            if (K && novr9 == 0 && maxsub <= t9i_wave16_max()) {
+            /* record sort: the wave16 sub-sort counts the ties itself
+             * (and leaves tie-free sub-buckets' keys unwritten) when it
+             * sorts every sub-bucket; otherwise the caller counts */
+            u32* tcount = nullptr;
+            if constexpr (HAS_VAL) {
+                if (d_ntied && novr9 == 0 &&
+                    t9i_lds_wave16() && maxsub <= t9i_wave16_max()) {
+                    tcount = d_ntied;
+                    HIP_TRY(hipMemsetAsync(tcount, 0, 4, s));
+                    if (tie_counted) *tie_counted = 1;
+                }
+            }
+            if (K && tcount) {
                 u64 bnd[T9_OVERLAP_MAXK + 1];
                 bnd[0] = 0;
                 bnd[K] = n;
@@ -1170,7 +1203,6 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                     int rc = t9i_overlap_init(ctx);
                     if (rc) return rc;
                     hipStream_t sb = ctx->ov_stream;
-                    HIP_TRY(hipMemsetAsync(ov->d_ntied, 0, 4, s));
                     u32 done = 0;
                     for (u32 c = 0; c < K; ++c) {
                         const u64 a = bnd[c], b = bnd[c + 1];
@@ -1179,19 +1211,14 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                         const u32 sub1 = (u32)((u64)(c + 1) * NSUB9 / K);
                         t9i_launch_wave16_sub<HAS_VAL>(
                             sub1 - sub0, maxsub, s, d_keys, d_vals,
-                            w.sub_start + sub0, w.sub_n + sub0);
+                            w.sub_start + sub0, w.sub_n + sub0, tcount);
                         T9_LAUNCH_CHECK();
-                        /* no comparison across the chunk edge: adjacent
-                         * sub-buckets differ in their top 17 key bits */
-                        rc = t9i_count_tied_acc(d_keys + a, b - a,
-                                                ov->d_ntied, s);
-                        if (rc) return rc;
                         HIP_TRY(hipEventRecord(ctx->ov_ev[c], s));
                         HIP_TRY(hipStreamWaitEvent(sb, ctx->ov_ev[c], 0));
                         rc = t9i_gather_chunk(
                             ov->recs, d_vals + a, b - a, n,
                             ov->out + a * (u64)ov->rec_words * 4,
-                            ov->d_ntied, sb);
+                            tcount, sb);
                         if (rc) return rc;
                         ++done;
                     }
@@ -1207,7 +1234,8 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                 if (t9i_lds_wave16() && maxsub <= t9i_wave16_max())
                     t9i_launch_wave16_sub<HAS_VAL>((u32)NSUB9, maxsub, s,
                                                    d_keys, d_vals,
-                                                   w.sub_start, w.sub_n);
+                                                   w.sub_start, w.sub_n,
+                                                   tcount);
                 else if (t9i_lds_bitonic())
                     t9i_launch_bitonic_sub<HAS_VAL>((u32)NSUB9, maxsub, s,
                                                     d_keys, d_vals,
@@ -1513,14 +1541,21 @@ extern "C" int t9i_sort_pairs_msb(t9_context* ctx, u64* d_keys,
  * returned by t9i_msb_pass1_hist. iota_vals: d_vals holds nothing yet —
  * the payload is the element's index and pass 1 produces it. ov (may be
  * null): record-sort request that may run the chunked sort -> gather
- * pipeline (ov->chunks != 0 on return: output gathered, ties counted
- * into ov->d_ntied, caller's stream joined). */
+ * pipeline (ov->chunks != 0 on return: output gathered, caller's stream
+ * joined). d_ntied (may be null) marks a record sort: where the wave16
+ * sub-sort sorted every sub-bucket, *tie_counted = 1 and *d_ntied holds the
+ * number of keys equal to their left neighbour, and only sub-buckets with
+ * a tie have their sorted keys written (k_wave16_sort_sub); otherwise
+ * *tie_counted = 0, d_keys is fully sorted and the caller counts. */
 extern "C" int t9i_sort_pairs_msb_ph(t9_context* ctx, u64* d_keys,
                                      u32* d_vals, u64 n,
                                      void* d_workspace, void* stream,
-                                     int iota_vals, t9_overlap_req* ov) {
+                                     int iota_vals, t9_overlap_req* ov,
+                                     u32* d_ntied, int* tie_counted) {
+    if (tie_counted) *tie_counted = 0;
     return sort_msb_impl<true>(ctx, d_keys, d_keys, d_vals, n, d_workspace,
-                               stream, true, ov, iota_vals != 0);
+                               stream, true, ov, iota_vals != 0, d_ntied,
+                               tie_counted);
 }
 
 extern "C" u32* t9i_msb_pass1_hist(void* d_workspace, u64 n) {

@@ -53,6 +53,7 @@ _SIGS = {
     "t9_sort_records": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
     "t9_sort_records_keyle": (i32, [vp, vp, vp, u64, u32, vp, vp]),
     "t9_sort_last_schedule": (i32, [vp]),
+    "t9_sort_last_tiecount": (i32, [vp]),
     "t9_extract_key64_le": (i32, [vp, vp, u64, u32, u32, vp, vp, vp]),
     "t9_classify_u64": (i32, [vp, vp, u64, u64, vp, vp, u32, vp, vp, vp]),
     "t9_classify_rec": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, u32, u32,
@@ -140,6 +141,14 @@ class Native:
         k = self._lib.t9_sort_last_schedule(self.ctx)
         if k < 0:
             raise T9Error(f"t9_sort_last_schedule failed rc={k}")
+        return k
+
+    def sort_last_tiecount(self):
+        """1 = the sub-bucket sort of the last record sort counted the
+        equal-key neighbours itself; 0 = a standalone pass did."""
+        k = self._lib.t9_sort_last_tiecount(self.ctx)
+        if k < 0:
+            raise T9Error(f"t9_sort_last_tiecount failed rc={k}")
         return k
 
     # perf registry functions take no context argument
