@@ -4,8 +4,8 @@
  * thrill/api/dia.hpp (Sort :798-937, ReduceByKey via ReducePair
  * :241-463, Generate api/generate.hpp:37, Size api/size.hpp:28,
  * AllGather api/all_gather.hpp) restricted to the GPU-executable contract:
- * fixed-size POD items, byte-lexicographic (or u64) key order, u64 sum
- * reduction. There is NO CPU execution path here — without a GPU,
+ * fixed-size POD items, byte-lexicographic (or u64) key order, 64-bit
+ * sum / min / max reduction. There is NO CPU execution path here — without a GPU,
  * Context construction fails (the CPU restatement lives in oracle/ and is
  * test infrastructure).
  *
@@ -451,8 +451,11 @@ public:
     //! user's reduce_function is additive on the counter — verified by
     //! ALGEBRAIC PROBING (the functor is a pure function of POD-ish pairs:
     //! it is evaluated on sample values and must return the counter sum,
-    //! the shape word_count.hpp:50-53 has); a non-additive functor falls
-    //! back to GPU grouping + a host fold with the user's functor.
+    //! the shape word_count.hpp:50-53 has). min and max on the counter,
+    //! with the key preserved, are recognised the same way and run on the
+    //! device through t9_reduce128_*_op (a signed counter in signed
+    //! order); a functor that is none of the three falls back to a host
+    //! fold with the user's functor.
     template <typename KeyExtractor, typename ReduceFn>
     DIA<ValueType> ReduceByKey(const KeyExtractor& key_ex,
                                const ReduceFn& red) const;
@@ -637,6 +640,155 @@ inline DIA<KeyValue> ReducePair(const DIA<KeyValue>& input,
     return FromVector(ctx, out);
 }
 
+//! The reduce functions that run on the device (t9_reduce_*_op): the
+//! reference takes any associative (V, V) -> V
+//! (core/reduce_probing_hash_table.hpp:233); these three have a native
+//! 64-bit atomic.
+enum class ReduceOp { Sum, Min, Max };
+
+namespace detail {
+
+//! Classify a reduce function by ALGEBRAIC PROBING: `apply(a, b)` — the
+//! user's functor seen as (u64 bits, u64 bits) -> u64 bits — is evaluated
+//! on operand pairs that tell sum, min and max apart (swapped operands, an
+//! equal pair, a wide value, and a pair whose order differs between signed
+//! and unsigned reading) and must agree with one operator on all of them.
+//! Returns false for a functor that is none of the three.
+template <typename Apply>
+bool classify_reduce(const Apply& apply, bool is_signed, ReduceOp* op) {
+    static const uint64_t probes[][2] = {
+        { 3, 17 }, { 17, 3 }, { 5, 5 }, { 1ull << 40, 7 }, { 0, 9 },
+        { ~0ull - 4, 2 },   // signed: -5 vs 2
+    };
+    bool sum = true, mn = true, mx = true;
+    for (const auto& p : probes) {
+        const uint64_t a = p[0], b = p[1], r = apply(a, b);
+        const bool a_less = is_signed ? (int64_t)a < (int64_t)b : a < b;
+        sum = sum && r == a + b;
+        mn = mn && r == (a_less ? a : b);
+        mx = mx && r == (a_less ? b : a);
+    }
+    if (sum) *op = ReduceOp::Sum;
+    else if (mn) *op = ReduceOp::Min;
+    else if (mx) *op = ReduceOp::Max;
+    return sum || mn || mx;
+}
+
+inline int native_op(ReduceOp op) {
+    return op == ReduceOp::Sum ? T9_OP_SUM
+         : op == ReduceOp::Min ? T9_OP_MIN : T9_OP_MAX;
+}
+
+} // namespace detail
+
+//! ReducePair with a reduce function — the reference's signature
+//! (api/reduce_by_key.hpp:393-463). The functor is probed on
+//! (u64, u64) -> u64 and must be +, min or max; the reduce then runs on
+//! the device (t9_reduce_*_op). Anything else throws
+//! std::invalid_argument: there is no host fold here.
+template <typename ReduceFn,
+          typename = decltype(std::declval<const ReduceFn&>()(
+              uint64_t(), uint64_t()))>
+DIA<KeyValue> ReducePair(const DIA<KeyValue>& input, const ReduceFn& red,
+                         uint64_t salt = 0) {
+    using KV = KeyValue;
+    ReduceOp rop;
+    if (!detail::classify_reduce(
+            [&](uint64_t a, uint64_t b) { return (uint64_t)red(a, b); },
+            false, &rop))
+        throw std::invalid_argument(
+            "ReducePair: the reduce function is none of +, min, max");
+    const int op = detail::native_op(rop);
+    Context& ctx = input.context();
+    size_t n = input.Size();
+    DeviceBuf dk(n * 8), dv(n * 8), didx(n * 4);
+    if (n) {
+        T9_DIA_TRY(t9_extract_key64_le(ctx.native(),
+                                       (const uint8_t*)input.device_ptr(),
+                                       n, 16, 0, (uint64_t*)dk.ptr,
+                                       (uint32_t*)didx.ptr, ctx.stream()));
+        T9_DIA_TRY(t9_extract_key64_le(ctx.native(),
+                                       (const uint8_t*)input.device_ptr(),
+                                       n, 16, 8, (uint64_t*)dv.ptr,
+                                       (uint32_t*)didx.ptr, ctx.stream()));
+    }
+    uint64_t cap = 1024;
+    while (cap < 2 * n + 2) cap <<= 1;   // no grow/spill: size for 2x
+    DeviceBuf tbl(2 * (cap + 1) * 8);
+    DeviceBuf ok((cap + 1) * 8), ov((cap + 1) * 8);
+    DeviceBuf derr(4), dn(8);
+    hipStream_t s = ctx.stream();
+    T9_DIA_TRY(t9_reduce_init_op(ctx.native(), (uint64_t*)tbl.ptr, cap, op,
+                                 T9_VAL_U64, s));
+    T9_DIA_TRY(t9_reduce_build_op(ctx.native(), (const uint64_t*)dk.ptr,
+                                  (const uint64_t*)dv.ptr, n,
+                                  (uint64_t*)tbl.ptr, cap, salt, op,
+                                  T9_VAL_U64, (uint32_t*)derr.ptr, s));
+    T9_DIA_TRY(t9_reduce_drain_op(ctx.native(), (const uint64_t*)tbl.ptr,
+                                  cap, op, T9_VAL_U64, (uint64_t*)ok.ptr,
+                                  (uint64_t*)ov.ptr, (uint64_t*)dn.ptr, s));
+    uint64_t m = 0;
+    uint32_t err = 0;
+    T9_DIA_HIP(hipMemcpy(&m, dn.ptr, 8, hipMemcpyDeviceToHost));
+    T9_DIA_HIP(hipMemcpy(&err, derr.ptr, 4, hipMemcpyDeviceToHost));
+    if (err) throw std::runtime_error("ReducePair: table overflow");
+    std::vector<uint64_t> rk(m), rv(m);
+    if (m) {
+        T9_DIA_HIP(hipMemcpy(rk.data(), ok.ptr, m * 8,
+                             hipMemcpyDeviceToHost));
+        T9_DIA_HIP(hipMemcpy(rv.data(), ov.ptr, m * 8,
+                             hipMemcpyDeviceToHost));
+    }
+    std::vector<KV> out(m);
+    for (size_t i = 0; i < m; ++i) out[i] = KV{ rk[i], rv[i] };
+    return FromVector(ctx, out);
+}
+
+//! ReduceToIndex — reference api/dia.hpp:1346-1351: keys are indices in
+//! [0, size); entry i of the result is the reduced value of key i, or
+//! `neutral` if no item has that key (the neutral element is not folded
+//! in — core/reduce_by_index_post_phase.hpp:150-172). Runs over
+//! t9_reduce_by_index_op with a probed +, min or max functor; anything
+//! else throws std::invalid_argument, a key >= size std::out_of_range.
+//! Deviation from the reference: it returns the whole reduced ITEMS (and a
+//! neutral item) in index order; this surface returns the u64 VALUES, the
+//! key being the position.
+template <typename ReduceFn>
+DIA<uint64_t> ReduceToIndex(const DIA<KeyValue>& input, const ReduceFn& red,
+                            size_t size, uint64_t neutral = 0) {
+    ReduceOp rop;
+    if (!detail::classify_reduce(
+            [&](uint64_t a, uint64_t b) { return (uint64_t)red(a, b); },
+            false, &rop))
+        throw std::invalid_argument(
+            "ReduceToIndex: the reduce function is none of +, min, max");
+    const int op = detail::native_op(rop);
+    Context& ctx = input.context();
+    const size_t n = input.Size();
+    auto dense = std::make_shared<DeviceBuf>(size * 8);
+    if (size == 0) return DIA<uint64_t>(&ctx, dense, 0);
+    DeviceBuf dk(n * 8), dv(n * 8), didx(n * 4);
+    if (n) {
+        T9_DIA_TRY(t9_extract_key64_le(ctx.native(),
+                                       (const uint8_t*)input.device_ptr(),
+                                       n, 16, 0, (uint64_t*)dk.ptr,
+                                       (uint32_t*)didx.ptr, ctx.stream()));
+        T9_DIA_TRY(t9_extract_key64_le(ctx.native(),
+                                       (const uint8_t*)input.device_ptr(),
+                                       n, 16, 8, (uint64_t*)dv.ptr,
+                                       (uint32_t*)didx.ptr, ctx.stream()));
+    }
+    DeviceBuf ws(t9_reduce_by_index_op_workspace(size)), derr(4);
+    T9_DIA_TRY(t9_reduce_by_index_op(
+        ctx.native(), (const uint64_t*)dk.ptr, (const uint64_t*)dv.ptr, n,
+        0, size, op, T9_VAL_U64, neutral, (uint64_t*)dense->ptr,
+        (uint32_t*)derr.ptr, ws.ptr, ctx.stream()));
+    uint32_t err = 0;
+    T9_DIA_HIP(hipMemcpy(&err, derr.ptr, 4, hipMemcpyDeviceToHost));
+    if (err) throw std::out_of_range("ReduceToIndex: key >= size");
+    return DIA<uint64_t>(&ctx, dense, size);
+}
+
 namespace detail {
 
 //! the framework's string hash pair: fnv-1a under two bases, mixed by
@@ -703,6 +855,23 @@ DIA<ValueType> DIA<ValueType>::ReduceByKey(const KeyExtractor& key_ex,
         }
     }
 
+    // not additive: is it min or max on .second with .first preserved?
+    // Those run on the device too (t9_reduce128_*_op); a signed Count
+    // reduces in two's-complement order.
+    ReduceOp rop = ReduceOp::Sum;
+    bool first_kept = true;
+    const bool minmax =
+        !additive &&
+        detail::classify_reduce(
+            [&](uint64_t a, uint64_t b) {
+                Pair r = red(Pair{ "probe", (Count)a },
+                             Pair{ "probe", (Count)b });
+                first_kept = first_kept && r.first == "probe";
+                return (uint64_t)r.second;
+            },
+            std::is_signed<Count>::value, &rop) &&
+        first_kept && rop != ReduceOp::Sum;
+
     // dictionary-encode: word -> (h1, h2); keep the decode map. The
     // decode key folds (h1, h2) into one u64 — a fold collision
     // (p ~= 2^-64 per pair) would mis-map a word at DECODE time only;
@@ -765,10 +934,56 @@ DIA<ValueType> DIA<ValueType>::ReduceByKey(const KeyExtractor& key_ex,
                 decode.at(r1[i] ^ (r2[i] << 1 | r2[i] >> 63)),
                 (Count)rv[i] });
     }
+    else if (n && minmax) {
+        // GPU 128-bit composite min/max-reduce
+        const int op = detail::native_op(rop);
+        const int vt = std::is_signed<Count>::value ? T9_VAL_I64
+                                                    : T9_VAL_U64;
+        DeviceBuf d1(n * 8), d2(n * 8), dv(n * 8);
+        T9_DIA_HIP(hipMemcpy(d1.ptr, k1.data(), n * 8,
+                             hipMemcpyHostToDevice));
+        T9_DIA_HIP(hipMemcpy(d2.ptr, k2.data(), n * 8,
+                             hipMemcpyHostToDevice));
+        T9_DIA_HIP(hipMemcpy(dv.ptr, vals.data(), n * 8,
+                             hipMemcpyHostToDevice));
+        uint64_t cap = 1024;
+        while (cap < 2 * n + 2) cap <<= 1;
+        DeviceBuf tbl(3 * cap * 8), o1(cap * 8), o2(cap * 8), ov(cap * 8);
+        DeviceBuf derr(4), dn(8);
+        hipStream_t s = ctx_->stream();
+        T9_DIA_TRY(t9_reduce128_init_op(ctx_->native(), (uint64_t*)tbl.ptr,
+                                        cap, op, vt, s));
+        T9_DIA_TRY(t9_reduce128_build_op(
+            ctx_->native(), (const uint64_t*)d1.ptr,
+            (const uint64_t*)d2.ptr, (const uint64_t*)dv.ptr, n,
+            (uint64_t*)tbl.ptr, cap, 0, op, vt, (uint32_t*)derr.ptr, s));
+        T9_DIA_TRY(t9_reduce128_drain_op(
+            ctx_->native(), (const uint64_t*)tbl.ptr, cap, op, vt,
+            (uint64_t*)o1.ptr, (uint64_t*)o2.ptr, (uint64_t*)ov.ptr,
+            (uint64_t*)dn.ptr, s));
+        uint64_t m = 0;
+        uint32_t err = 0;
+        T9_DIA_HIP(hipMemcpy(&m, dn.ptr, 8, hipMemcpyDeviceToHost));
+        T9_DIA_HIP(hipMemcpy(&err, derr.ptr, 4, hipMemcpyDeviceToHost));
+        if (err) throw std::runtime_error("ReduceByKey: table overflow");
+        std::vector<uint64_t> r1(m), r2(m), rv(m);
+        if (m) {
+            T9_DIA_HIP(hipMemcpy(r1.data(), o1.ptr, m * 8,
+                                 hipMemcpyDeviceToHost));
+            T9_DIA_HIP(hipMemcpy(r2.data(), o2.ptr, m * 8,
+                                 hipMemcpyDeviceToHost));
+            T9_DIA_HIP(hipMemcpy(rv.data(), ov.ptr, m * 8,
+                                 hipMemcpyDeviceToHost));
+        }
+        out.reserve(m);
+        for (uint64_t i = 0; i < m; ++i)
+            out.push_back(Pair{
+                decode.at(r1[i] ^ (r2[i] << 1 | r2[i] >> 63)),
+                (Count)rv[i] });
+    }
     else if (n) {
-        // non-additive reduce function: host fold with the user's functor
-        // (grouping semantics preserved; the hot path is the additive
-        // word_count shape above)
+        // a reduce function that is none of +, min, max: host fold with
+        // the user's functor (grouping semantics preserved)
         std::unordered_map<uint64_t, Pair> acc;
         for (size_t i = 0; i < n; ++i) {
             const uint64_t h = k1[i] ^ (k2[i] << 1 | k2[i] >> 63);
@@ -1083,7 +1298,9 @@ using api::GroupByKey;
 using api::KeyValue;
 using api::Merge;
 using api::ReadBinary;
+using api::ReduceOp;
 using api::ReducePair;
+using api::ReduceToIndex;
 using api::Run;
 
 } // namespace t9

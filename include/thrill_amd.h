@@ -341,6 +341,88 @@ int t9_index_bucket(t9_context* ctx, const uint64_t* d_keys, uint64_t n,
                     uint32_t* d_bucket, uint64_t* d_counts,
                     uint32_t* d_error, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * Reduce operators — the three tables above with a selectable reduce
+ * function. The reference's reduce_function is any associative
+ * (V, V) -> V (core/reduce_probing_hash_table.hpp:233); the operators
+ * with a native 64-bit atomic run here: SUM, MIN, MAX, over values read
+ * as u64, i64 (two's-complement order) or f64. F64 order is the IEEE-754
+ * totalOrder of the bit patterns: -NaN < -inf < ... < -0.0 < +0.0 < ...
+ * < +inf < +NaN — total and deterministic, so results are bit-exact
+ * however the atomics interleave. SUM is the wrapping 64-bit add (the
+ * same for U64 and I64); SUM with F64 is T9_EINVAL, because a floating
+ * atomic sum depends on arrival order (DESIGN.md "Reduce operators").
+ *
+ * Each _op function takes the parameters of the function it parallels
+ * plus (op, vtype). Layouts, capacity rules, the sentinel-key aux slot,
+ * probe order, salt, the error model and the stream contract are
+ * unchanged, so t9_reduce128_lookup works on a table built with any
+ * operator. What differs is the value word: init_op fills it with the
+ * operator's identity (0 for SUM, all-ones for MIN, 0 for MAX), and for
+ * MIN and MAX the table holds ENCODED values — I64: bits ^ 1<<63; F64:
+ * bits ^ (sign ? ~0 : 1<<63) — which order as unsigned integers;
+ * drain_op decodes. A table carries no operator tag: init_op, build_op
+ * and drain_op must be called with the same (op, vtype); mixing them, or
+ * mixing _op calls with the plain ones on one table, is a caller error.
+ *
+ * Every _op function validates op, vtype, pointers and the power-of-two
+ * capacity before any device call. The operator path instantiates fewer
+ * kernel variants than the plain one: T9_LDS_SLOTS / T9_LDS128_SLOTS
+ * select 1024 (<= 1024) or 4096 slots, T9_REDUCE_GRID,
+ * T9_REDUCE_READFIRST and T9_R128_READFIRST are honoured,
+ * T9_REDUCE_COMBINE and T9_REDUCE_WAVECOMB are served by the LDS variant
+ * (same layout, same result), and T9_R128_STRIDE=4 is refused with
+ * T9_EINVAL by every t9_reduce128_*_op call.
+ * ------------------------------------------------------------------ */
+typedef enum { T9_OP_SUM = 0, T9_OP_MIN = 1, T9_OP_MAX = 2 } t9_reduce_op;
+typedef enum { T9_VAL_U64 = 0, T9_VAL_I64 = 1, T9_VAL_F64 = 2 } t9_val_type;
+
+/* op / vtype are passed as int so that an out-of-range value is a
+ * T9_EINVAL, not undefined behaviour. Values travel as their 64-bit
+ * patterns in uint64_t arrays whatever vtype says. */
+int t9_reduce_init_op(t9_context* ctx, uint64_t* d_table, uint64_t capacity,
+                      int op, int vtype, void* stream);
+int t9_reduce_build_op(t9_context* ctx, const uint64_t* d_keys,
+                       const uint64_t* d_vals, uint64_t n,
+                       uint64_t* d_table, uint64_t capacity, uint64_t salt,
+                       int op, int vtype, uint32_t* d_error, void* stream);
+int t9_reduce_drain_op(t9_context* ctx, const uint64_t* d_table,
+                       uint64_t capacity, int op, int vtype,
+                       uint64_t* d_out_keys, uint64_t* d_out_vals,
+                       uint64_t* d_out_n, void* stream);
+
+/* d_vals == NULL ("every pair counts 1") is valid only with T9_OP_SUM;
+ * T9_EINVAL otherwise. */
+int t9_reduce128_init_op(t9_context* ctx, uint64_t* d_table,
+                         uint64_t capacity, int op, int vtype,
+                         void* stream);
+int t9_reduce128_build_op(t9_context* ctx, const uint64_t* d_k1,
+                          const uint64_t* d_k2, const uint64_t* d_vals,
+                          uint64_t n, uint64_t* d_table, uint64_t capacity,
+                          uint64_t salt, int op, int vtype,
+                          uint32_t* d_error, void* stream);
+int t9_reduce128_drain_op(t9_context* ctx, const uint64_t* d_table,
+                          uint64_t capacity, int op, int vtype,
+                          uint64_t* d_out_k1, uint64_t* d_out_k2,
+                          uint64_t* d_out_vals, uint64_t* d_out_n,
+                          void* stream);
+
+/* ReduceToIndex with an operator and a neutral element (reference
+ * api/dia.hpp:1346-1351): d_dense[i] is the fold of the values whose key
+ * is begin + i, or `neutral` if NO item has that key. The neutral element
+ * is not folded in (core/reduce_by_index_post_phase.hpp:150-172), and an
+ * index whose only values equal the operator's identity still yields that
+ * value: "untouched" is recorded in a bitmap in d_workspace
+ * (t9_reduce_by_index_op_workspace(size) bytes; pure host code).
+ * Out-of-range keys set d_error, as in t9_reduce_by_index. */
+uint64_t t9_reduce_by_index_op_workspace(uint64_t size);
+int t9_reduce_by_index_op(t9_context* ctx, const uint64_t* d_keys,
+                          const uint64_t* d_vals, uint64_t n,
+                          uint64_t begin, uint64_t size, int op, int vtype,
+                          uint64_t neutral, uint64_t* d_dense,
+                          uint32_t* d_error, void* d_workspace,
+                          void* stream);
+
 /* GroupByKey support (SURVEY.md §8f item 3 — thrill/api/group_by_key.hpp
  * is sort-based): the group index of a key-sorted array. d_unique[g] /
  * d_offsets[g] (ascending run starts) for g in [0, *d_count); d_count is

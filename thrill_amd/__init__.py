@@ -13,4 +13,6 @@ from .native import (  # noqa: F401
     lib_path,
     load_lib,
     Native,
+    T9_OP_SUM, T9_OP_MIN, T9_OP_MAX,
+    T9_VAL_U64, T9_VAL_I64, T9_VAL_F64,
 )

@@ -16,6 +16,12 @@ i32 = ctypes.c_int
 vp = ctypes.c_void_p
 
 
+# t9_reduce_op / t9_val_type of include/thrill_amd.h
+T9_OP_SUM, T9_OP_MIN, T9_OP_MAX = 0, 1, 2
+T9_VAL_U64, T9_VAL_I64, T9_VAL_F64 = 0, 1, 2
+T9_EINVAL = -22
+
+
 class T9Error(RuntimeError):
     pass
 
@@ -73,6 +79,18 @@ _SIGS = {
     "t9_reduce128_drain": (i32, [vp, vp, u64, vp, vp, vp, vp, vp]),
     "t9_reduce128_lookup": (i32, [vp, vp, vp, u64, vp, u64, u64, vp, vp]),
     "t9_hash2_of": (i32, [vp, vp, u64, vp, vp, vp]),
+    "t9_reduce_init_op": (i32, [vp, vp, u64, i32, i32, vp]),
+    "t9_reduce_build_op": (i32, [vp, vp, vp, u64, vp, u64, u64, i32, i32,
+                                 vp, vp]),
+    "t9_reduce_drain_op": (i32, [vp, vp, u64, i32, i32, vp, vp, vp, vp]),
+    "t9_reduce128_init_op": (i32, [vp, vp, u64, i32, i32, vp]),
+    "t9_reduce128_build_op": (i32, [vp, vp, vp, vp, u64, vp, u64, u64, i32,
+                                    i32, vp, vp]),
+    "t9_reduce128_drain_op": (i32, [vp, vp, u64, i32, i32, vp, vp, vp, vp,
+                                    vp]),
+    "t9_reduce_by_index_op_workspace": (u64, [u64]),
+    "t9_reduce_by_index_op": (i32, [vp, vp, vp, u64, u64, u64, i32, i32,
+                                    u64, vp, vp, vp, vp]),
     "t9_text_tokenize_workspace": (u64, [u64]),
     "t9_text_tokenize": (i32, [vp, vp, u64, vp, vp, vp, vp, vp]),
     "t9_text_hash2": (i32, [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]),

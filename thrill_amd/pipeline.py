@@ -311,6 +311,98 @@ class WordCount:
         self.nat.close()
 
 
+class ReducePairs:
+    """One rank's ReduceByKey of (u64 key, 64-bit value) pairs under a
+    reduce operator (T9_OP_SUM / MIN / MAX over T9_VAL_U64 / I64 / F64):
+    local pre-reduce with `op` -> hash partition
+    (core/reduce_functional.hpp:60-72) -> one all-to-all -> post-reduce
+    with the same `op`. The two-phase form needs only an associative and
+    commutative operator, which all three are. Same shape as
+    WordCount.step, including the single-rank early return and the
+    T9_FORCE_DIST branch."""
+
+    def __init__(self, op, vtype, rank=0, world=1, device=0):
+        self.nat = Native(device=device, rank=rank, world=world)
+        self.op, self.vtype = int(op), int(vtype)
+        self.rank, self.world = rank, world
+        if world > 1 and os.environ.get("T9_EXCHANGE", "t9") == "t9":
+            import torch.distributed as dist
+            bootstrap_comm(self.nat, dist, rank)
+
+    def _reduce(self, d_keys, d_vals, n, salt=0):
+        """(keys, vals, m) of the n pairs reduced with (op, vtype); the
+        table is sized for 2x the pair count (no grow/spill)."""
+        nat, s = self.nat, _stream()
+        cap = 1 << max(10, int(2 * n + 2 - 1).bit_length())
+        i64 = torch.int64
+        d_tbl = torch.empty(2 * (cap + 1), dtype=i64, device="cuda")
+        d_ok = torch.empty(cap + 1, dtype=i64, device="cuda")
+        d_ov = torch.empty(cap + 1, dtype=i64, device="cuda")
+        d_err = torch.empty(1, dtype=torch.int32, device="cuda")
+        d_n = torch.empty(1, dtype=i64, device="cuda")
+        nat.reduce_init_op(_ptr(d_tbl), cap, self.op, self.vtype, s)
+        nat.reduce_build_op(_ptr(d_keys), _ptr(d_vals), n, _ptr(d_tbl), cap,
+                            salt, self.op, self.vtype, _ptr(d_err), s)
+        nat.reduce_drain_op(_ptr(d_tbl), cap, self.op, self.vtype,
+                            _ptr(d_ok), _ptr(d_ov), _ptr(d_n), s)
+        m = int(d_n.cpu().item())
+        if int(d_err.cpu().item()):
+            raise T9Error("ReducePairs: reduce table overflow")
+        return d_ok[:m].clone(), d_ov[:m].clone(), m
+
+    def step(self, d_keys, d_vals):
+        """One full ReduceByKey of this rank's pairs (device tensors of
+        8-byte elements, equal length). Returns (keys tensor, vals tensor,
+        m) of this rank's final pairs, in arbitrary order."""
+        if d_keys.numel() != d_vals.numel() or \
+                d_keys.element_size() != 8 or d_vals.element_size() != 8:
+            raise T9Error("ReducePairs: keys/vals must be equal-length "
+                          "tensors of 8-byte elements")
+        nat, s = self.nat, _stream()
+        keys, vals, m = self._reduce(d_keys, d_vals, d_keys.numel())
+        if self.world == 1 and not os.environ.get("T9_FORCE_DIST"):
+            return keys, vals, m
+
+        import torch.distributed as dist
+        p = self.world
+        d_bucket = torch.empty(max(m, 1), dtype=torch.int32, device="cuda")
+        d_counts = torch.empty(p, dtype=torch.int64, device="cuda")
+        nat.hash_bucket(_ptr(keys), m, 0, p, _ptr(d_bucket),
+                        _ptr(d_counts), s)
+        d_perm = torch.empty(max(m, 1), dtype=torch.int32, device="cuda")
+        d_offs = torch.empty(p + 1, dtype=torch.int64, device="cuda")
+        d_ws = torch.empty(max(int(nat.ws("partition_idx", m)), 256),
+                           dtype=torch.uint8, device="cuda")
+        nat.partition_idx(_ptr(d_bucket), m, p, _ptr(d_perm), _ptr(d_offs),
+                          _ptr(d_ws), s)
+        ks = torch.empty(max(m, 1), dtype=torch.int64, device="cuda")
+        vs = torch.empty(max(m, 1), dtype=torch.int64, device="cuda")
+        if m:
+            nat.gather_records(_ptr(keys), _ptr(d_perm), m, 8, _ptr(ks), s)
+            nat.gather_records(_ptr(vals), _ptr(d_perm), m, 8, _ptr(vs), s)
+        send_counts = d_counts.cpu().numpy().astype(np.int64)
+        recv_counts = exchange_counts(dist, send_counts, self.rank,
+                                      self.world)
+        n_recv = int(recv_counts.sum())
+        exchange = os.environ.get("T9_EXCHANGE", "t9")
+        recv = []
+        for a in (ks, vs):
+            r = torch.empty(max(n_recv, 1), dtype=torch.int64,
+                            device="cuda")
+            if exchange == "t9" or self.world == 1:
+                a2a(nat, a, send_counts, r, recv_counts, 8)
+            else:
+                dist.all_to_all_single(
+                    r[:n_recv], a[:m],
+                    output_split_sizes=recv_counts.tolist(),
+                    input_split_sizes=send_counts.tolist())
+            recv.append(r)
+        return self._reduce(recv[0], recv[1], n_recv)
+
+    def close(self):
+        self.nat.close()
+
+
 class TeraSort:
     """One rank's TeraSort state. world==1: pure local sort. world>1:
     sample -> splitters -> classify -> partition -> all-to-all -> local
