@@ -25,6 +25,12 @@
  * TextWordCount takes raw text bytes instead: tokenizing, hashing,
  * reducing and choosing one spelling per word all run on the device
  * (DESIGN.md "Real text: device tokenizer and hasher").
+ *
+ * PrefixSum / ExPrefixSum and the Sum / Min / Max / AllReduce actions run
+ * on the device (t9_scan_u64 / t9_scan_kv / t9_fold_u64) for a probed +,
+ * min or max over 64-bit scalar items and for the { b.key, op(a.value,
+ * b.value) } shape over KeyValue; everything else folds on the host in the
+ * reference's own order (DESIGN.md "Scan family").
  */
 #pragma once
 
@@ -460,6 +466,64 @@ public:
     DIA<ValueType> ReduceByKey(const KeyExtractor& key_ex,
                                const ReduceFn& red) const;
 
+    //! PrefixSum / ExPrefixSum — reference api/dia.hpp:1837-1868,
+    //! api/prefix_sum.hpp:92-110: out[i] = initial ⊕ x[0] ⊕ … ⊕ x[i]
+    //! (inclusive) or … ⊕ x[i-1] (exclusive, out[0] = initial). The
+    //! functor is classified by ALGEBRAIC PROBING, as ReduceByKey's is.
+    //! Items of type uint64_t / size_t, int64_t or double with a functor
+    //! that is +, min or max (but not + over double) are scanned on the
+    //! device by t9_scan_u64 and stay there; DIA<KeyValue>::PrefixSum with
+    //! a functor of the shape { b.key, op(a.value, b.value) } — the
+    //! prefix_doubling.cpp:346-351 idiom — runs t9_scan_kv. min and max
+    //! over double follow the IEEE-754 totalOrder of the device
+    //! (-0.0 < +0.0, NaNs at the ends). Everything else (a foreign
+    //! functor, + over double, ExPrefixSum over KeyValue, other item
+    //! types) folds sequentially on the host in the reference's own
+    //! evaluation order.
+    template <typename SumFunction = std::plus<ValueType> >
+    DIA PrefixSum(const SumFunction& sum_function = SumFunction(),
+                  const ValueType& initial_element = ValueType()) const {
+        return ScanImpl(sum_function, initial_element, false);
+    }
+    template <typename SumFunction = std::plus<ValueType> >
+    DIA ExPrefixSum(const SumFunction& sum_function = SumFunction(),
+                    const ValueType& initial_element = ValueType()) const {
+        return ScanImpl(sum_function, initial_element, true);
+    }
+
+    //! AllReduce / Sum / Min / Max actions — reference api/dia.hpp:599-752,
+    //! api/all_reduce.hpp: without an initial value the fold starts from
+    //! the first item and an empty DIA yields ValueType()
+    //! (all_reduce.hpp:39-46); with one, it is folded in once, in front.
+    //! Device execution (t9_fold_u64) under the conditions of PrefixSum's
+    //! scalar case, host fold otherwise.
+    template <typename ReduceFunction>
+    ValueType AllReduce(const ReduceFunction& reduce_function) const {
+        return FoldImpl(reduce_function, nullptr);
+    }
+    template <typename ReduceFunction>
+    ValueType AllReduce(const ReduceFunction& reduce_function,
+                        const ValueType& initial_value) const {
+        return FoldImpl(reduce_function, &initial_value);
+    }
+    template <typename SumFunction = std::plus<ValueType> >
+    ValueType Sum(const SumFunction& sum_function = SumFunction()) const {
+        return FoldImpl(sum_function, nullptr);
+    }
+    template <typename SumFunction = std::plus<ValueType> >
+    ValueType Sum(const SumFunction& sum_function,
+                  const ValueType& initial_value) const {
+        return FoldImpl(sum_function, &initial_value);
+    }
+    ValueType Min() const { return FoldImpl(MinFn(), nullptr); }
+    ValueType Min(const ValueType& initial_value) const {
+        return FoldImpl(MinFn(), &initial_value);
+    }
+    ValueType Max() const { return FoldImpl(MaxFn(), nullptr); }
+    ValueType Max(const ValueType& initial_value) const {
+        return FoldImpl(MaxFn(), &initial_value);
+    }
+
     //! WriteBinary — reference api/write_binary.hpp: the items as packed
     //! binary (the POD raw-copy wire format, data/serialization.hpp:35-48),
     //! one file per worker: pathbase + zero-padded rank. The on-disk bytes
@@ -501,6 +565,22 @@ public:
 
 private:
     DIA SortImpl() const;
+
+    //! common::minimum / maximum of the reference (std::min / std::max)
+    struct MinFn {
+        ValueType operator()(const ValueType& a, const ValueType& b) const {
+            return std::min(a, b);
+        }
+    };
+    struct MaxFn {
+        ValueType operator()(const ValueType& a, const ValueType& b) const {
+            return std::max(a, b);
+        }
+    };
+    template <typename Fn>
+    DIA ScanImpl(const Fn& fn, const ValueType& initial, bool exclusive) const;
+    template <typename Fn>
+    ValueType FoldImpl(const Fn& fn, const ValueType* initial) const;
 
     template <typename T>
     friend DIA<T> FromVector(Context&, const std::vector<T>&);
@@ -787,6 +867,174 @@ DIA<uint64_t> ReduceToIndex(const DIA<KeyValue>& input, const ReduceFn& red,
     T9_DIA_HIP(hipMemcpy(&err, derr.ptr, 4, hipMemcpyDeviceToHost));
     if (err) throw std::out_of_range("ReduceToIndex: key >= size");
     return DIA<uint64_t>(&ctx, dense, size);
+}
+
+namespace detail {
+
+//! 64-bit scalars the scan family runs on the device, and their
+//! t9_val_type
+template <typename T>
+struct scan_scalar {
+    static constexpr bool value =
+        (std::is_integral<T>::value && sizeof(T) == 8 &&
+         !std::is_same<T, bool>::value) ||
+        std::is_same<T, double>::value;
+    static constexpr int vtype =
+        std::is_same<T, double>::value ? T9_VAL_F64
+        : std::is_signed<T>::value     ? T9_VAL_I64
+                                       : T9_VAL_U64;
+};
+
+template <typename T>
+inline uint64_t scan_bits(const T& v) {
+    static_assert(sizeof(T) == 8, "64-bit scalar");
+    uint64_t b;
+    std::memcpy(&b, &v, 8);
+    return b;
+}
+template <typename T>
+inline T scan_value(uint64_t b) {
+    static_assert(sizeof(T) == 8, "64-bit scalar");
+    T v;
+    std::memcpy(&v, &b, 8);
+    return v;
+}
+
+//! classify_reduce for a functor over a 64-bit scalar. Integers are
+//! probed on their bit patterns in their own signedness; doubles are
+//! probed ON DOUBLES, including {-2, -1}, whose order is the opposite of
+//! the integer order of the bits, signed or unsigned.
+template <typename T, typename Fn>
+bool classify_scalar(const Fn& fn, ReduceOp* op) {
+    if constexpr (std::is_same<T, double>::value) {
+        static const double probes[][2] = {
+            { 3.0, 17.0 }, { 17.0, 3.0 }, { 5.0, 5.0 }, { -2.0, -1.0 },
+            { 1e300, 7.0 }, { 0.5, -0.25 },
+        };
+        bool sum = true, mn = true, mx = true;
+        for (const auto& p : probes) {
+            const double a = p[0], b = p[1], r = (double)fn(a, b);
+            sum = sum && r == a + b;
+            mn = mn && r == (a < b ? a : b);
+            mx = mx && r == (a < b ? b : a);
+        }
+        if (sum) *op = ReduceOp::Sum;
+        else if (mn) *op = ReduceOp::Min;
+        else if (mx) *op = ReduceOp::Max;
+        return sum || mn || mx;
+    }
+    else {
+        return classify_reduce(
+            [&](uint64_t a, uint64_t b) {
+                return (uint64_t)(T)fn((T)a, (T)b);
+            },
+            std::is_signed<T>::value, op);
+    }
+}
+
+//! is fn(a, b) == { b.key, op(a.value, b.value) } with op one of +, min,
+//! max? Probed on pairs with distinct keys.
+template <typename Fn>
+bool classify_kv_scan(const Fn& fn, ReduceOp* op) {
+    bool key_kept = true;
+    const bool known = classify_reduce(
+        [&](uint64_t a, uint64_t b) {
+            const KeyValue r = fn(KeyValue{ 0x1111, a },
+                                  KeyValue{ 0x2222 + a, b });
+            key_kept = key_kept && r.key == 0x2222 + a;
+            return r.value;
+        },
+        false, op);
+    return known && key_kept;
+}
+
+} // namespace detail
+
+template <typename ValueType>
+template <typename Fn>
+DIA<ValueType> DIA<ValueType>::ScanImpl(const Fn& fn,
+                                        const ValueType& initial,
+                                        bool exclusive) const {
+    if constexpr (detail::scan_scalar<ValueType>::value) {
+        ReduceOp rop;
+        constexpr int vt = detail::scan_scalar<ValueType>::vtype;
+        if (!hvec_ && detail::classify_scalar<ValueType>(fn, &rop) &&
+            !(rop == ReduceOp::Sum && vt == T9_VAL_F64)) {
+            auto out = std::make_shared<DeviceBuf>(n_ * 8);
+            if (n_) {
+                DeviceBuf ws(t9_scan_workspace(n_));
+                T9_DIA_TRY(t9_scan_u64(
+                    ctx_->native(), (const uint64_t*)buf_->ptr,
+                    (uint64_t*)out->ptr, n_, detail::native_op(rop), vt,
+                    exclusive ? 1 : 0, detail::scan_bits(initial), nullptr,
+                    ws.ptr, ctx_->stream()));
+                T9_DIA_HIP(hipStreamSynchronize(ctx_->stream()));
+            }
+            return DIA(ctx_, out, n_);
+        }
+    }
+    if constexpr (std::is_same<ValueType, KeyValue>::value) {
+        ReduceOp rop;
+        if (!exclusive && !hvec_ && detail::classify_kv_scan(fn, &rop)) {
+            auto out = std::make_shared<DeviceBuf>(n_ * 16);
+            if (n_) {
+                DeviceBuf ws(t9_scan_workspace(n_));
+                T9_DIA_TRY(t9_scan_kv(
+                    ctx_->native(), (const uint8_t*)buf_->ptr,
+                    (uint8_t*)out->ptr, n_, detail::native_op(rop),
+                    T9_VAL_U64, initial.value, nullptr, ws.ptr,
+                    ctx_->stream()));
+                T9_DIA_HIP(hipStreamSynchronize(ctx_->stream()));
+            }
+            return DIA(ctx_, out, n_);
+        }
+    }
+    // host fold with the user's functor, in the reference's order
+    // (api/prefix_sum.hpp:92-110)
+    const auto items = AllGather();
+    std::vector<ValueType> out;
+    out.reserve(items.size());
+    ValueType sum = initial;
+    for (const auto& x : items) {
+        if (exclusive) out.push_back(sum);
+        sum = fn(sum, x);
+        if (!exclusive) out.push_back(sum);
+    }
+    return FromVector(*ctx_, out);
+}
+
+template <typename ValueType>
+template <typename Fn>
+ValueType DIA<ValueType>::FoldImpl(const Fn& fn,
+                                   const ValueType* initial) const {
+    if (n_ == 0) return initial ? *initial : ValueType();
+    if constexpr (detail::scan_scalar<ValueType>::value) {
+        ReduceOp rop;
+        constexpr int vt = detail::scan_scalar<ValueType>::vtype;
+        if (!hvec_ && detail::classify_scalar<ValueType>(fn, &rop) &&
+            !(rop == ReduceOp::Sum && vt == T9_VAL_F64)) {
+            DeviceBuf ws(t9_scan_workspace(n_)), dres(8);
+            T9_DIA_TRY(t9_fold_u64(ctx_->native(),
+                                   (const uint64_t*)buf_->ptr, n_, 1,
+                                   detail::native_op(rop), vt,
+                                   (uint64_t*)dres.ptr, ws.ptr,
+                                   ctx_->stream()));
+            uint64_t bits = 0;
+            T9_DIA_HIP(hipMemcpyAsync(&bits, dres.ptr, 8,
+                                      hipMemcpyDeviceToHost,
+                                      ctx_->stream()));
+            T9_DIA_HIP(hipStreamSynchronize(ctx_->stream()));
+            const ValueType r = detail::scan_value<ValueType>(bits);
+            return initial ? (ValueType)fn(*initial, r) : r;
+        }
+    }
+    // host fold (api/all_reduce.hpp:56-64): from the initial value if
+    // there is one, else from the first item
+    const auto items = AllGather();
+    size_t i = 0;
+    ValueType sum = initial ? *initial : items[i++];
+    for (; i < items.size(); ++i) sum = fn(sum, items[i]);
+    return sum;
 }
 
 namespace detail {

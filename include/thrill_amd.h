@@ -423,6 +423,66 @@ int t9_reduce_by_index_op(t9_context* ctx, const uint64_t* d_keys,
                           uint32_t* d_error, void* d_workspace,
                           void* stream);
 
+/* ------------------------------------------------------------------ *
+ * Scan family — PrefixSum / ExPrefixSum and the fold behind the Sum / Min
+ * / Max actions (reference api/prefix_sum.hpp:92-110, api/all_reduce.hpp)
+ * with the operators and value types of "Reduce operators" above. With ⊕
+ * the operator and `initial` a 64-bit pattern read as vtype:
+ *   inclusive: out[i] = initial ⊕ x[0] ⊕ … ⊕ x[i]
+ *   exclusive: out[0] = initial, out[i] = initial ⊕ x[0] ⊕ … ⊕ x[i-1]
+ * SUM is the wrapping 64-bit add (the same for U64 and I64); MIN and MAX
+ * order values as unsigned, two's-complement or IEEE-754 totalOrder; SUM
+ * with F64 is T9_EINVAL. Every result is bit-exact and does not depend on
+ * how the work is split (DESIGN.md "Scan family").
+ *
+ * A scan is three launches on `stream` — fold every tile, scan the tile
+ * totals, scan every tile from its carry — and no block waits on another.
+ * t9_scan_geometry reports the tile size in elements and how many tile
+ * totals one block of the middle pass covers (above that count a second
+ * level runs); pure host code. t9_scan_workspace(n) bytes of d_workspace
+ * serve t9_scan_u64, t9_scan_kv and t9_fold_u64 on n elements; pure host
+ * code. The workspace need not be zeroed, nothing in it survives a call,
+ * and it should be 16-byte aligned (hipMalloc memory is).
+ *
+ * d_out == d_in (in place) is allowed; otherwise d_in is not written.
+ * Pointers aligned to 16 bytes get 16-byte accesses; 8-byte alignment is
+ * enough for correctness. If d_total is non-NULL it receives the fold of
+ * the n inputs WITHOUT `initial`.
+ *
+ * t9_scan_kv scans 16-byte {u64 key, 64-bit value} pairs, inclusive only:
+ * the key is copied through and the value word is scanned — the
+ * PrefixSum([](a, b){ return { b.key, op(a.value, b.value) }; }) idiom of
+ * examples/suffix_sorting/prefix_doubling.cpp:346-351; `initial` seeds the
+ * value word. An exclusive scan over pairs would shift the keys and is not
+ * offered.
+ *
+ * t9_fold_u64 folds n values read every stride_words u64 words (1 =
+ * contiguous, 2 = the value word of n pairs: pass the address of the
+ * first pair) into *d_out (device u64).
+ *
+ * Validation comes before any device call; each of these is T9_EINVAL:
+ * op or vtype out of range, SUM with F64, exclusive not 0 or 1,
+ * stride_words not 1 or 2, a NULL in, out or workspace pointer with
+ * n > 0, NULL d_out of the fold, 2^31 tiles or more. With n == 0, d_total
+ * and the fold's d_out receive the operator's identity as a value of
+ * vtype: 0 for SUM; for MIN the top of the order (all-ones, INT64_MAX,
+ * the largest +NaN); for MAX the bottom (0, INT64_MIN, the largest -NaN).
+ * With n == 0 and d_total == NULL a scan returns T9_OK without touching
+ * the device.
+ * ------------------------------------------------------------------ */
+void t9_scan_geometry(uint32_t* tile_elems, uint32_t* partials_per_block);
+uint64_t t9_scan_workspace(uint64_t n);
+int t9_scan_u64(t9_context* ctx, const uint64_t* d_in, uint64_t* d_out,
+                uint64_t n, int op, int vtype, int exclusive,
+                uint64_t initial, uint64_t* d_total, void* d_workspace,
+                void* stream);
+int t9_scan_kv(t9_context* ctx, const uint8_t* d_in, uint8_t* d_out,
+               uint64_t n, int op, int vtype, uint64_t initial,
+               uint64_t* d_total, void* d_workspace, void* stream);
+int t9_fold_u64(t9_context* ctx, const uint64_t* d_in, uint64_t n,
+                uint32_t stride_words, int op, int vtype, uint64_t* d_out,
+                void* d_workspace, void* stream);
+
 /* GroupByKey support (SURVEY.md §8f item 3 — thrill/api/group_by_key.hpp
  * is sort-based): the group index of a key-sorted array. d_unique[g] /
  * d_offsets[g] (ascending run starts) for g in [0, *d_count); d_count is
@@ -458,7 +518,9 @@ int t9_zipf_tokens(t9_context* ctx, uint64_t* d_out, const double* d_cdf,
 /* ------------------------------------------------------------------ *
  * Optional per-kernel-class HIP event timing (off by default) for the
  * bench harness's roofline measurement. Classes: "pair_scatter",
- * "keys_scatter", "hist_pairs", "hist_keys", "extract", "gather".
+ * "keys_scatter", "hist_pairs", "hist_keys", "extract", "gather",
+ * "reduce_build_op", "scan" (one t9_scan_* or t9_fold_u64 call, all its
+ * launches) and "scan_pass2" (the middle pass of a scan alone).
  * ------------------------------------------------------------------ */
 int t9_perf_enable(int on);
 int t9_perf_read(const char* kernel_class, double* total_ms,

@@ -16,3 +16,12 @@ from .native import (  # noqa: F401
     T9_OP_SUM, T9_OP_MIN, T9_OP_MAX,
     T9_VAL_U64, T9_VAL_I64, T9_VAL_F64,
 )
+
+
+def __getattr__(name):
+    # the scan family's host layer lives in pipeline.py, which needs
+    # torch: resolved on first use so that `import thrill_amd` stays light
+    if name in ("PrefixSum", "scan_carry", "scan_identity"):
+        from . import pipeline
+        return getattr(pipeline, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

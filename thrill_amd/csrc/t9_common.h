@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "thrill_amd.h"   /* t9_reduce_op / t9_val_type for t9_enc/t9_dec */
+
 using u8 = uint8_t;
 using u16 = uint16_t;
 using u32 = uint32_t;
@@ -89,6 +91,20 @@ __host__ __device__ inline u64 t9_hash128to64(u64 upper, u64 lower) {
     b ^= (b >> 47);
     b *= k;
     return b;
+}
+
+#define T9_MSB 0x8000000000000000ull
+
+/* order-preserving encode/decode; SUM works on raw bits */
+__host__ __device__ inline u64 t9_enc(u64 b, int op, int vtype) {
+    if (op == T9_OP_SUM || vtype == T9_VAL_U64) return b;
+    if (vtype == T9_VAL_I64) return b ^ T9_MSB;
+    return b ^ ((b >> 63) ? ~0ull : T9_MSB);
+}
+__host__ __device__ inline u64 t9_dec(u64 e, int op, int vtype) {
+    if (op == T9_OP_SUM || vtype == T9_VAL_U64) return e;
+    if (vtype == T9_VAL_I64) return e ^ T9_MSB;
+    return e ^ ((e >> 63) ? T9_MSB : ~0ull);
 }
 
 static inline u64 t9_ceil_div(u64 a, u64 b) { return (a + b - 1) / b; }

@@ -33,21 +33,12 @@
 #include <cstdlib>
 
 #define T9_EMPTY 0xFFFFFFFFFFFFFFFFull
-#define T9_MSB 0x8000000000000000ull
 
 namespace {
 
-/* order-preserving encode/decode; SUM works on raw bits */
-__host__ __device__ inline u64 t9_enc(u64 b, int op, int vtype) {
-    if (op == T9_OP_SUM || vtype == T9_VAL_U64) return b;
-    if (vtype == T9_VAL_I64) return b ^ T9_MSB;
-    return b ^ ((b >> 63) ? ~0ull : T9_MSB);
-}
-__host__ __device__ inline u64 t9_dec(u64 e, int op, int vtype) {
-    if (op == T9_OP_SUM || vtype == T9_VAL_U64) return e;
-    if (vtype == T9_VAL_I64) return e ^ T9_MSB;
-    return e ^ ((e >> 63) ? T9_MSB : ~0ull);
-}
+/* t9_enc / t9_dec, the order-preserving value encoding, live in
+ * t9_common.h (shared with t9_scan.hip) */
+
 /* the operator's identity in the (encoded) table domain */
 inline u64 ident_of(int op) {
     return op == T9_OP_MIN ? ~0ull : 0ull;

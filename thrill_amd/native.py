@@ -91,6 +91,11 @@ _SIGS = {
     "t9_reduce_by_index_op_workspace": (u64, [u64]),
     "t9_reduce_by_index_op": (i32, [vp, vp, vp, u64, u64, u64, i32, i32,
                                     u64, vp, vp, vp, vp]),
+    "t9_scan_geometry": (None, [ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+    "t9_scan_workspace": (u64, [u64]),
+    "t9_scan_u64": (i32, [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, vp]),
+    "t9_scan_kv": (i32, [vp, vp, vp, u64, i32, i32, u64, vp, vp, vp]),
+    "t9_fold_u64": (i32, [vp, vp, u64, u32, i32, i32, vp, vp, vp]),
     "t9_text_tokenize_workspace": (u64, [u64]),
     "t9_text_tokenize": (i32, [vp, vp, u64, vp, vp, vp, vp, vp]),
     "t9_text_hash2": (i32, [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]),
@@ -188,6 +193,13 @@ class Native:
     def ws(self, name, *args):
         """workspace byte queries (no ctx argument)."""
         return getattr(self._lib, f"t9_{name}_workspace")(*args)
+
+    def scan_geometry(self):
+        """(tile elements, tile totals per block of the middle pass) of
+        the scan family; no ctx argument, pure host code."""
+        t, p = u32(), u32()
+        self._lib.t9_scan_geometry(ctypes.byref(t), ctypes.byref(p))
+        return t.value, p.value
 
     def version(self):
         return self._lib.t9_version().decode()

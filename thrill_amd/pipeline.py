@@ -19,7 +19,8 @@ import os
 import numpy as np
 import torch
 
-from .native import Native, T9Error
+from .native import (Native, T9Error, T9_OP_SUM, T9_OP_MIN, T9_OP_MAX,
+                     T9_VAL_U64, T9_VAL_I64, T9_VAL_F64)
 
 REC = 100  # TeraSort record bytes (examples/terasort/terasort.cpp:31-43)
 
@@ -398,6 +399,156 @@ class ReducePairs:
                     input_split_sizes=send_counts.tolist())
             recv.append(r)
         return self._reduce(recv[0], recv[1], n_recv)
+
+    def close(self):
+        self.nat.close()
+
+_M64 = (1 << 64) - 1
+_MSB = 1 << 63
+
+
+def _scan_enc(b, op, vtype):
+    """t9_enc of t9_common.h on a Python int pattern."""
+    b &= _M64
+    if op == T9_OP_SUM or vtype == T9_VAL_U64:
+        return b
+    if vtype == T9_VAL_I64:
+        return b ^ _MSB
+    return b ^ (_M64 if b >> 63 else _MSB)
+
+
+def _scan_dec(e, op, vtype):
+    if op == T9_OP_SUM or vtype == T9_VAL_U64:
+        return e
+    if vtype == T9_VAL_I64:
+        return e ^ _MSB
+    return e ^ (_MSB if e >> 63 else _M64)
+
+
+def _scan_check(op, vtype):
+    if op not in (T9_OP_SUM, T9_OP_MIN, T9_OP_MAX) or \
+            vtype not in (T9_VAL_U64, T9_VAL_I64, T9_VAL_F64) or \
+            (op == T9_OP_SUM and vtype == T9_VAL_F64):
+        raise T9Error(f"scan: unsupported (op, vtype) = ({op}, {vtype})")
+
+
+def scan_identity(op, vtype):
+    """64-bit pattern of the operator's identity as a value of vtype: what
+    the fold of nothing is (an empty shard's total)."""
+    _scan_check(op, vtype)
+    return _scan_dec(_M64 if op == T9_OP_MIN else 0, op, vtype)
+
+
+def scan_carry(totals, rank, op, vtype, initial):
+    """64-bit pattern of initial ⊕ totals[0] ⊕ … ⊕ totals[rank-1]: the
+    value rank `rank` seeds its local scan with, the reference's
+    net.ExPrefixSum(local_sum, fn, initial) (api/prefix_sum.hpp:85-90).
+    totals are the per-rank folds as 64-bit patterns (an empty shard's is
+    scan_identity). Host arithmetic in the kernels' encoding, so the
+    result is the bit pattern the device would compute. Pure: no torch,
+    no GPU."""
+    _scan_check(op, vtype)
+    acc = _scan_enc(int(initial), op, vtype)
+    for t in list(totals)[:rank]:
+        e = _scan_enc(int(t), op, vtype)
+        if op == T9_OP_SUM:
+            acc = (acc + e) & _M64
+        elif op == T9_OP_MIN:
+            acc = min(acc, e)
+        else:
+            acc = max(acc, e)
+    return _scan_dec(acc, op, vtype)
+
+
+def _to_i64(p):
+    return p - (1 << 64) if p >> 63 else p
+
+
+def exchange_totals(dist, local, world):
+    """every rank's 64-bit pattern, by rank: one all-gather of 8 bytes
+    each over the control plane, as exchange_counts does for counts."""
+    dev = _ctl_device(dist)
+    mine = torch.tensor([_to_i64(int(local) & _M64)], dtype=torch.int64,
+                        device=dev)
+    rows = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(rows, mine)
+    return [int(r.cpu().item()) & _M64 for r in rows]
+
+
+class PrefixSum:
+    """One rank's PrefixSum / ExPrefixSum of 64-bit values under a scan
+    operator (T9_OP_SUM / MIN / MAX over T9_VAL_U64 / I64 / F64), the
+    reference's PrefixSumNode (api/prefix_sum.hpp:60-118). Single rank:
+    one t9_scan_u64. world > 1 (or T9_FORCE_DIST): fold the shard
+    (t9_fold_u64), all-gather the per-rank totals over the control plane,
+    scan_carry, then t9_scan_u64 seeded with that carry. Same shape as
+    ReducePairs, including the T9_FORCE_DIST branch. `initial` is a 64-bit
+    pattern."""
+
+    def __init__(self, op, vtype, exclusive=False, initial=0, rank=0,
+                 world=1, device=0):
+        _scan_check(int(op), int(vtype))
+        self.nat = Native(device=device, rank=rank, world=world)
+        self.op, self.vtype = int(op), int(vtype)
+        self.exclusive = 1 if exclusive else 0
+        self.initial = int(initial) & _M64
+        self.rank, self.world = rank, world
+
+    def _check(self, d_vals):
+        if d_vals.dim() != 1 or d_vals.element_size() != 8 or \
+                not d_vals.is_contiguous():
+            raise T9Error("PrefixSum: values must be a contiguous 1-d "
+                          "tensor of 8-byte elements")
+
+    def _ws(self, n):
+        return torch.empty(max(int(self.nat.ws("scan", n)), 256),
+                           dtype=torch.uint8, device="cuda")
+
+    def _dist(self):
+        return self.world > 1 or bool(os.environ.get("T9_FORCE_DIST"))
+
+    def _fold_local(self, d_vals):
+        """this shard's fold as a pattern (identity for an empty shard)."""
+        n = d_vals.numel()
+        d_tot = torch.empty(1, dtype=torch.int64, device="cuda")
+        d_ws = self._ws(n)
+        self.nat.fold_u64(_ptr(d_vals) if n else None, n, 1, self.op,
+                          self.vtype, _ptr(d_tot), _ptr(d_ws), _stream())
+        return int(d_tot.cpu().item()) & _M64
+
+    def _totals(self, local):
+        import torch.distributed as dist
+        return exchange_totals(dist, local, self.world)
+
+    def step(self, d_vals):
+        """The scan of this rank's values (a device tensor of 8-byte
+        elements) as a new tensor of the same dtype; with world > 1 the
+        shards are consecutive by rank."""
+        self._check(d_vals)
+        n = d_vals.numel()
+        init = self.initial
+        if self._dist():
+            totals = self._totals(self._fold_local(d_vals))
+            init = scan_carry(totals, self.rank, self.op, self.vtype,
+                              self.initial)
+        d_out = torch.empty_like(d_vals)
+        if n:
+            d_ws = self._ws(n)
+            self.nat.scan_u64(_ptr(d_vals), _ptr(d_out), n, self.op,
+                              self.vtype, self.exclusive, init, None,
+                              _ptr(d_ws), _stream())
+        return d_out
+
+    def reduce(self, d_vals):
+        """The fold of every rank's values as a Python int (the 64-bit
+        pattern), without `initial`: the Sum / Min / Max actions. The fold
+        of nothing is scan_identity(op, vtype)."""
+        self._check(d_vals)
+        local = self._fold_local(d_vals)
+        if not self._dist():
+            return local
+        return scan_carry(self._totals(local), self.world, self.op,
+                          self.vtype, scan_identity(self.op, self.vtype))
 
     def close(self):
         self.nat.close()
