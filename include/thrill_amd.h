@@ -90,7 +90,8 @@ int t9_extract_key64_le(t9_context* ctx, const uint8_t* d_recs, uint64_t n,
                         uint32_t rec_size, uint32_t key_off,
                         uint64_t* d_keys, uint32_t* d_idx, void* stream);
 
-/* out[i] = recs[idx[i]] for fixed-size records (rec_size % 4 == 0). */
+/* out[i] = recs[idx[i]] for fixed-size records; rec_size is a positive
+ * multiple of 4 (T9_EINVAL otherwise, before any device call). */
 int t9_gather_records(t9_context* ctx, const uint8_t* d_recs,
                       const uint32_t* d_idx, uint64_t n, uint32_t rec_size,
                       uint8_t* d_out, void* stream);

@@ -476,6 +476,7 @@ def test_merge_u64_parity(nat, oracle, na, nb):
 
 def test_merge_u64_tie_source_order(nat):
     # equal keys: all of a's precede b's — distinguish via known layout
+    # (equal u64 keys are identical bits: the source order is not observable)
     a = np.array([5, 5, 7], dtype=np.uint64)
     b = np.array([5, 6, 7, 7], dtype=np.uint64)
     da, db = G.dev(a), G.dev(b)

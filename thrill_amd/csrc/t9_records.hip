@@ -668,7 +668,8 @@ int t9_extract_key64_le(t9_context* ctx, const u8* d_recs, u64 n,
 int t9_gather_records(t9_context* ctx, const u8* d_recs, const u32* d_idx,
                       u64 n, u32 rec_size, u8* d_out, void* stream) {
     (void)ctx;
-    if (!d_recs || !d_idx || !d_out || rec_size % 4) return T9_EINVAL;
+    if (!d_recs || !d_idx || !d_out || rec_size == 0 || rec_size % 4)
+        return T9_EINVAL;
     if (n == 0) return T9_OK;
     const u32 rw = rec_size / 4;
     hipStream_t s = (hipStream_t)stream;
