@@ -66,11 +66,10 @@ __device__ inline void t9_hist_ballot_add(u32* __restrict__ s_cnt, u32 d,
         atomicAdd(&s_cnt[d], (u32)__popcll(m));
 }
 
-/* 512-thread (8-wave) wave-autonomous scatter, always global re-read:
- * doubles waves/SIMD to 4 at the same LDS footprint — the PMC-measured
- * limiter of the 256-thread version was 81% SQ_WAIT_ANY at 2 waves/SIMD.
- * Digit recomputed from the L1/L2-resident re-read instead of an LDS
- * cache. */
+/* Wave-autonomous stable scatter of one TILE by BLOCK threads (512 or
+ * 1024; the name dates from the first, 512-thread form), always global
+ * re-read: the digit is recomputed from the L1/L2-resident re-read of the
+ * key instead of an LDS cache. */
 /* REC_WORDS != 0: "fused extract" mode — in_keys is the packed record
  * array (REC_WORDS u32 words per record); the big-endian u64 key prefix
  * is built from the record bytes and the payload is the record index
@@ -80,22 +79,34 @@ __device__ inline void t9_hist_ballot_add(u32* __restrict__ s_cnt, u32 d,
  * REC_WORDS mode, but the keys are the packed u64 array — pass 1 after the
  * fused extract + histogram, which then need not write the index iota
  * for this kernel to read back (in_vals is not touched). */
+/* LDS is what bounds the residency: at the 8192 tile a block holds 74 KiB,
+ * so two 1024-thread blocks (8 waves/SIMD) share a CU's 160 KiB and one
+ * runs while the other waits on its loads or drains its stores. To fit,
+ * the ranks, the tile positions and the output positions live in
+ * registers, one u16 array holds the per-wave counts and then, scanned in
+ * place, the per-wave offsets, and the keys and then the values are
+ * reordered through the same buffer. */
 template <int TILE, int BLOCK, bool HAS_KEY, bool HAS_VAL,
           int REC_WORDS = 0, bool IOTA_VAL = false>
-__global__ __launch_bounds__(BLOCK, 4) void k_scatter_wave512(
+__global__ __launch_bounds__(BLOCK, 8) void k_scatter_wave512(
     const u64* __restrict__ in_keys, const u32* __restrict__ in_vals,
     u64* __restrict__ out_keys, u32* __restrict__ out_vals,
     const u32* __restrict__ offs, u64 n, u32 shift) {
     constexpr int NW = BLOCK / 64;
     constexpr int SUB = TILE / NW;
-    constexpr int GROUPS = SUB / 64;
+    constexpr int GROUPS = SUB / 64;   /* = TILE / BLOCK: elements per lane */
+    static_assert(HAS_KEY, "the store phase reads the digit from the key");
+    static_assert(TILE % BLOCK == 0 && SUB % 64 == 0, "whole groups");
     const u32* rec32 = (const u32*)in_keys;
-    __shared__ u64 s_okeys[HAS_KEY ? TILE : 1];
-    __shared__ u32 s_ovals[HAS_VAL ? TILE : 1];
-    __shared__ u16 s_rank[TILE];
-    __shared__ u8 s_digof[TILE];
-    __shared__ u32 s_wcnt[NW * T9_RADIX];
-    __shared__ u32 s_woff[NW * T9_RADIX];
+    /* keys in round 1, values in round 2 (bytes: may alias both) */
+    __shared__ __align__(16) u8 s_raw[TILE * 8];
+    u64* const s_okeys = (u64*)s_raw;
+    u32* const s_ovals = (u32*)s_raw;
+    /* per wave and digit: first the count (<= SUB, a wave's sub-tile),
+     * then the elements of that digit in the waves before (<= TILE - SUB);
+     * a rank is < SUB and a tile position < TILE. All fit 16 bits. */
+    static_assert(TILE <= 65535, "u16 counts and offsets");
+    __shared__ u16 s_wcnt[NW * T9_RADIX];
     __shared__ u32 s_start[T9_RADIX];
     __shared__ u32 s_goff[T9_RADIX];
 
@@ -105,9 +116,13 @@ __global__ __launch_bounds__(BLOCK, 4) void k_scatter_wave512(
 
     if (tid < T9_RADIX)
         s_goff[tid] = offs[(u64)blockIdx.x * T9_RADIX + tid];
-    for (u32 t = lane; t < T9_RADIX; t += 64) s_wcnt[wave * T9_RADIX + t] = 0;
+    u16* const wc = s_wcnt + wave * T9_RADIX;
+    for (u32 t = lane; t < T9_RADIX; t += 64) wc[t] = 0;
 
+    /* rank inside the wave's sub-tile, then position inside the tile */
+    u32 pos[GROUPS];
     const u32 wbase = wave * SUB;
+#pragma unroll
     for (int g = 0; g < GROUPS; ++g) {
         const u32 i = wbase + g * 64 + lane;
         const bool valid = i < tn;
@@ -125,33 +140,30 @@ __global__ __launch_bounds__(BLOCK, 4) void k_scatter_wave512(
             m &= ((d >> bit) & 1u) ? bb : ~bb;
         }
         const u32 wr = (u32)__popcll(m & ((1ull << lane) - 1ull));
-        const u32 before = valid ? s_wcnt[wave * T9_RADIX + d] : 0;
-        if (valid) {
-            s_rank[i] = (u16)(before + wr);
-            if (wr == 0)
-                s_wcnt[wave * T9_RADIX + d] = before + (u32)__popcll(m);
-        }
+        const u32 before = valid ? (u32)wc[d] : 0;
+        pos[g] = before + wr;
+        if (valid && wr == 0) wc[d] = (u16)(before + (u32)__popcll(m));
     }
     __syncthreads();
 
-    /* combine (threads 0..255 own digit tid) */
+    /* combine (threads 0..255 own digit tid): counts -> offsets in place */
     if (tid < T9_RADIX) {
         u32 run = 0;
         for (int w = 0; w < NW; ++w) {
-            s_woff[w * T9_RADIX + tid] = run;   /* wave-relative for now */
-            run += s_wcnt[w * T9_RADIX + tid];
+            const u32 c = s_wcnt[w * T9_RADIX + tid];
+            s_wcnt[w * T9_RADIX + tid] = (u16)run;
+            run += c;
         }
         s_start[tid] = run;
     }
     __syncthreads();
     t9_scan256_onewave(s_start, tid);   /* s_start: totals -> exclusive */
     __syncthreads();
-    if (tid < T9_RADIX) {
-        const u32 excl = s_start[tid];
-        for (int w = 0; w < NW; ++w) s_woff[w * T9_RADIX + tid] += excl;
-    }
-    __syncthreads();
 
+    /* round 1: keys */
+    constexpr bool LOAD_VAL = HAS_VAL && !REC_WORDS && !IOTA_VAL;
+    u32 val[LOAD_VAL ? GROUPS : 1];
+#pragma unroll
     for (int g = 0; g < GROUPS; ++g) {
         const u32 i = wbase + g * 64 + lane;
         if (i < tn) {
@@ -163,29 +175,46 @@ __global__ __launch_bounds__(BLOCK, 4) void k_scatter_wave512(
                     __builtin_bswap32((u32)w1);
             }
             else {
-                k = HAS_KEY ? in_keys[base + i] : 0;
+                k = in_keys[base + i];
             }
+            if constexpr (LOAD_VAL) val[g] = in_vals[base + i];
             const u32 d = (u32)(k >> shift) & 255u;
-            const u32 pos = s_woff[wave * T9_RADIX + d] + s_rank[i];
-            if (HAS_KEY) s_okeys[pos] = k;
-            if (HAS_VAL)
-                s_ovals[pos] =
-                    (REC_WORDS || IOTA_VAL) ? (u32)(base + i)
-                                            : in_vals[base + i];
-            s_digof[pos] = (u8)d;
+            pos[g] += s_start[d] + (u32)wc[d];
+            s_okeys[pos[g]] = k;
         }
     }
     __syncthreads();
 
-    constexpr int CHUNKS = TILE / BLOCK;
-    for (int c = 0; c < CHUNKS; ++c) {
+    /* an output position is below the end of the output array, which the
+     * u32 offsets in offs already address */
+    u32 gpos[GROUPS];
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c) {
         const u32 j = c * BLOCK + tid;
         if (j < tn) {
-            const u32 d = s_digof[j];
-            const u64 gpos = (u64)s_goff[d] + (j - s_start[d]);
-            if (HAS_KEY) out_keys[gpos] = s_okeys[j];
-            if (HAS_VAL) out_vals[gpos] = s_ovals[j];
+            const u64 k = s_okeys[j];
+            const u32 d = (u32)(k >> shift) & 255u;
+            gpos[c] = s_goff[d] + (j - s_start[d]);
+            out_keys[gpos[c]] = k;
         }
+    }
+    if (!HAS_VAL) return;
+    __syncthreads();
+
+    /* round 2: values, through the same buffer */
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+        const u32 i = wbase + g * 64 + lane;
+        if (i < tn) {
+            if constexpr (LOAD_VAL) s_ovals[pos[g]] = val[g];
+            else s_ovals[pos[g]] = (u32)(base + i);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c) {
+        const u32 j = c * BLOCK + tid;
+        if (j < tn) out_vals[gpos[c]] = s_ovals[j];
     }
 }
 
