@@ -108,10 +108,33 @@ __global__ __launch_bounds__(256) void k_seg_scan9(
     }
 }
 
-/* segmented 1024-thread scatter over 512 digits; u16 count/offset rows,
- * digit recomputed from the staged key in the write phase */
+/* Segmented 1024-thread stable scatter over 512 digits, one 8192-key tile
+ * of the padded pass-1 output per block.
+ *
+ * LDS bounds the residency: the block holds exactly 80 KiB (the 64 KiB
+ * reorder buffer and the 16 KiB count array, nothing else), so two blocks
+ * (8 waves/SIMD) share a CU's 160 KiB and one runs while the other waits
+ * on its loads or drains its stores. To fit, each lane keeps its 8 keys,
+ * their ranks, tile positions and output positions in registers (every key
+ * is read from global memory once); one u16 array holds the per-wave
+ * counts and then, in place, the tile position at which each wave's run of
+ * each digit starts; the keys and then the values are reordered through
+ * the same buffer; the tile's bucket is found from abase in global memory
+ * (no LDS copy); and the two small arrays that are left overlay bytes that
+ * are dead while they live:
+ *
+ *   s_raw    keys from barrier C (round 1 writes them) to barrier F (every
+ *            thread holds its 8 reordered keys in registers), values from
+ *            barrier F on;
+ *   s_wtot   s_raw[0, 32): written between barriers A and B, read between
+ *            B and C, before the first key is written to s_raw;
+ *   s_wcnt   counts and tile positions up to barrier D, after which no
+ *            count is read again;
+ *   s_delta  s_wcnt[0, 2048): written between barriers D and E, read
+ *            between E and F.
+ */
 template <bool HAS_VAL>
-__global__ __launch_bounds__(1024, 4) void k_scatter_seg9(
+__global__ __launch_bounds__(1024, 8) void k_scatter_seg9(
     const u64* __restrict__ in_keys, const u32* __restrict__ in_vals,
     const u32* __restrict__ abase, const u32* __restrict__ bucket_n,
     u64* __restrict__ out_keys, u32* __restrict__ out_vals,
@@ -119,92 +142,206 @@ __global__ __launch_bounds__(1024, 4) void k_scatter_seg9(
     constexpr int TILE = T9_MSB_TILE;
     constexpr int NW = 16;
     constexpr int SUB = TILE / NW;
-    constexpr int GROUPS = SUB / 64;
-    __shared__ u64 s_okeys[TILE];
-    __shared__ u32 s_ovals[HAS_VAL ? TILE : 1];
-    __shared__ u16 s_rank[TILE];
-    __shared__ u16 s_wcnt[NW * NDIG9];
-    __shared__ u16 s_woff[NW * NDIG9];
-    __shared__ u32 s_start[NDIG9];
-    __shared__ u32 s_goff[NDIG9];
-    __shared__ u32 s_abase[257];
+    constexpr int GROUPS = SUB / 64;   /* = TILE / 1024: keys per lane */
+    /* keys in round 1, values in round 2 */
+    __shared__ __align__(16) u8 s_raw[TILE * 8];
+    u64* const s_okeys = (u64*)s_raw;
+    u32* const s_ovals = (u32*)s_raw;
+    /* per wave and digit: first the count (<= SUB = 512, a wave's
+     * sub-tile), then the tile position of the wave's first key of that
+     * digit (<= 8191 where a key uses it, TILE where none does) */
+    static_assert(SUB <= 65535 && TILE <= 65535, "u16 counts and offsets");
+    static_assert(NW * 64 == 1024 && NDIG9 == 8 * 64,
+                  "one thread per key column, waves 0..7 own the digits");
+    __shared__ __align__(16) u16 s_wcnt[NW * NDIG9];
+    /* totals of the digits of waves 0..7, for the scan across them */
+    u32* const s_wtot = (u32*)s_raw;
+    /* per digit: output position of the digit's run minus its tile
+     * position; u32 arithmetic, the sum with a tile position is exact */
+    u32* const s_delta = (u32*)s_wcnt;
 
     const u32 tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (tid < 257) s_abase[tid] = abase[tid];
-    __syncthreads();
+    /* Which tile: blocks are dealt to the 8 XCDs in turn, so block b and
+     * b + 8 share an L2. Each XCD takes a contiguous eighth of the tiles:
+     * the tiles in flight on it are neighbours, mostly of one bucket, and
+     * the short digit runs (16 keys on average) that they append to the
+     * same sub-buckets meet in that L2 before they leave it. Any bijection
+     * is correct; this one is for speed only. */
+    const u32 xper = gridDim.x >> 3, xrem = gridDim.x & 7;
+    const u32 xcd = blockIdx.x & 7;
+    const u32 tile = xcd * xper + (xcd < xrem ? xcd : xrem) +
+                     (blockIdx.x >> 3);
     /* u64 guard before narrowing — see k_hist_seg9 */
-    const u64 tbase64 = (u64)blockIdx.x * TILE;
-    if (tbase64 >= s_abase[256]) return;
+    const u64 tbase64 = (u64)tile * TILE;
+    if (tbase64 >= abase[256]) return;
     const u32 tbase = (u32)tbase64;
-    const u32 b = bucket_of9(s_abase, tbase);
-    const u32 off_in_bucket = tbase - s_abase[b];
-    const u32 bn = bucket_n[b];
+
+    /* One round of loads, all in flight together: the lane's 8 keys, and
+     * abase and bucket_n, 4 entries a lane in every wave. The keys do not
+     * wait for the tile's length: a tile below abase[256] lies inside the
+     * padded pass-1 output whole, and what it holds past its length is
+     * read and never used. */
+    const u32 wbase = wave * SUB;
+    u64 key[GROUPS];
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g)
+        key[g] = in_keys[tbase + wbase + g * 64 + lane];
+    u32 ab[4], bnq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        ab[q] = abase[q * 64 + lane];
+        bnq[q] = bucket_n[q * 64 + lane];
+    }
+    u16* const wc = s_wcnt + wave * NDIG9;
+    for (u32 t = lane; t < NDIG9; t += 64) wc[t] = 0;
+
+    /* bucket of the tile: abase is non-decreasing with abase[0] = 0, so the
+     * last b with abase[b] <= tbase is the count of such entries less one
+     * (what bucket_of9 finds); no LDS copy, no barrier. Its base and count
+     * come from the lane that loaded them. */
+    u32 nle = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        nle += (u32)__popcll(__ballot(ab[q] <= tbase));
+    const u32 b = nle - 1, bq = b >> 6;
+    const u32 ab_b = (u32)__builtin_amdgcn_readlane(
+        (int)(bq == 0 ? ab[0] : bq == 1 ? ab[1] : bq == 2 ? ab[2] : ab[3]),
+        (int)(b & 63));
+    const u32 bn = (u32)__builtin_amdgcn_readlane(
+        (int)(bq == 0 ? bnq[0] : bq == 1 ? bnq[1] : bq == 2 ? bnq[2]
+                                                            : bnq[3]),
+        (int)(b & 63));
+    const u32 off_in_bucket = tbase - ab_b;
     const u32 tn = (bn > off_in_bucket)
                        ? ((bn - off_in_bucket < (u32)TILE)
                               ? bn - off_in_bucket
                               : (u32)TILE)
                        : 0;
+    if (tn == 0) return;   /* padding of an empty bucket tail: block-uniform */
 
-    if (tid < NDIG9)
-        s_goff[tid] = offs[(u64)blockIdx.x * NDIG9 + tid];
-    for (u32 t = lane; t < NDIG9; t += 64) s_wcnt[wave * NDIG9 + t] = 0;
-
-    const u32 wbase = wave * SUB;
+    /* rank inside the wave's sub-tile, then position inside the tile.
+     * differ = the lanes whose digit is not this lane's: bit by bit, the
+     * ballot of the bit, inverted for a lane whose own bit is set.
+     * Ranks (< 512) and tile positions (< 8192) are kept two to a
+     * register, in 16 bits each. */
+    u32 pos2[GROUPS / 2] = {};
+#pragma unroll
     for (int g = 0; g < GROUPS; ++g) {
         const u32 i = wbase + g * 64 + lane;
         const bool valid = i < tn;
-        u32 d = 0;
-        if (valid) d = (u32)(in_keys[tbase + i] >> 47) & 511u;
-        u64 m = __ballot(valid);
+        const u32 d = (u32)(key[g] >> 47) & 511u;
+        u32 dlo = 0, dhi = 0;
+#pragma unroll
         for (int bit = 0; bit < 9; ++bit) {
-            u64 bb = __ballot((d >> bit) & 1u);
-            m &= ((d >> bit) & 1u) ? bb : ~bb;
+            const u32 own = 0u - ((d >> bit) & 1u);   /* all ones or zero */
+            const u64 bb = __ballot(own != 0);
+            dlo |= (u32)bb ^ own;
+            dhi |= (u32)(bb >> 32) ^ own;
         }
+        const u64 m = __ballot(valid) & ~(((u64)dhi << 32) | dlo);
         const u32 wr = (u32)__popcll(m & ((1ull << lane) - 1ull));
-        const u32 before = valid ? (u32)s_wcnt[wave * NDIG9 + d] : 0;
-        if (valid) {
-            s_rank[i] = (u16)(before + wr);
-            if (wr == 0)
-                s_wcnt[wave * NDIG9 + d] =
-                    (u16)(before + (u32)__popcll(m));
-        }
+        const u32 before = wc[d];
+        pos2[g >> 1] |= (before + wr) << (16 * (g & 1));
+        if (valid && wr == 0) wc[d] = (u16)(before + (u32)__popcll(m));
     }
-    __syncthreads();
+    u32 goff = 0;   /* used after barrier B */
+    if (tid < NDIG9) goff = offs[(u64)tile * NDIG9 + tid];
+    __syncthreads();                                   /* A */
 
+    /* combine (waves 0..7, thread = digit): counts -> offsets inside the
+     * digit, in place; the digit totals are scanned in registers, wave by
+     * wave, and the wave totals go through s_wtot */
+    u32 excl = 0;
     if (tid < NDIG9) {
         u32 run = 0;
         for (int w = 0; w < NW; ++w) {
-            s_woff[w * NDIG9 + tid] = (u16)run;
-            run += s_wcnt[w * NDIG9 + tid];
+            const u32 c = s_wcnt[w * NDIG9 + tid];
+            s_wcnt[w * NDIG9 + tid] = (u16)run;
+            run += c;
         }
-        s_start[tid] = run;
+        u32 v = run;
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 y = __shfl_up(v, off);
+            if (lane >= (u32)off) v += y;
+        }
+        excl = v - run;
+        if (lane == 63) s_wtot[wave] = v;
     }
-    __syncthreads();
-    t9_scan_onewave<NDIG9>(s_start, tid);
-    __syncthreads();
+    __syncthreads();                                   /* B */
+    u32 delta = 0;
+    if (tid < NDIG9) {
+        u32 start = excl;   /* tile position of the digit's run */
+        for (u32 w = 0; w < wave; ++w) start += s_wtot[w];
+        for (int w = 0; w < NW; ++w)
+            s_wcnt[w * NDIG9 + tid] += (u16)start;
+        delta = goff - start;
+    }
+    __syncthreads();                                   /* C */
 
+    /* the values, used in round 2: in flight behind round 1 and the
+     * barriers up to F, and for a whole tile like the keys */
+    u32 val[HAS_VAL ? GROUPS : 1];
+    if constexpr (HAS_VAL) {
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g)
+            val[g] = in_vals[tbase + wbase + g * 64 + lane];
+    }
+
+    /* round 1: keys. Here and below only the LDS writes and the global
+     * stores are under a condition; the LDS reads run for a whole tile
+     * (past its length they fetch what is never used), so that they go out
+     * back to back and not one per branch. */
+#pragma unroll
     for (int g = 0; g < GROUPS; ++g) {
         const u32 i = wbase + g * 64 + lane;
-        if (i < tn) {
-            const u64 k = in_keys[tbase + i];
-            const u32 d = (u32)(k >> 47) & 511u;
-            const u32 pos = s_start[d] + (u32)s_woff[wave * NDIG9 + d] +
-                            s_rank[i];
-            s_okeys[pos] = k;
-            if (HAS_VAL) s_ovals[pos] = in_vals[tbase + i];
-        }
+        const u32 d = (u32)(key[g] >> 47) & 511u;
+        const u32 pos = ((pos2[g >> 1] >> (16 * (g & 1))) & 0xffffu) +
+                        (u32)wc[d];
+        if (i < tn) s_okeys[pos] = key[g];
+        pos2[g >> 1] += (u32)wc[d] << (16 * (g & 1));
     }
-    __syncthreads();
+    __syncthreads();                                   /* D */
+    if (tid < NDIG9) s_delta[tid] = delta;
+    __syncthreads();                                   /* E */
 
-    constexpr int CHUNKS = TILE / 1024;
-    for (int c = 0; c < CHUNKS; ++c) {
-        const u32 j = c * 1024 + tid;
-        if (j < tn) {
-            const u32 d = (u32)(s_okeys[j] >> 47) & 511u;
-            const u64 gpos = (u64)s_goff[d] + (j - s_start[d]);
-            out_keys[gpos] = s_okeys[j];
-            if (HAS_VAL) out_vals[gpos] = s_ovals[j];
+    /* the thread's 8 keys of the reordered tile and their output positions.
+     * An output position is below the end of the output array, which the
+     * u32 offsets in offs already address. */
+    u64 k[GROUPS];
+    u32 gpos[GROUPS];
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c) k[c] = s_okeys[c * 1024 + tid];
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c)
+        gpos[c] = s_delta[(u32)(k[c] >> 47) & 511u] + (c * 1024 + tid);
+    if constexpr (HAS_VAL) {
+        __syncthreads();                               /* F */
+        /* round 2: values, through the same buffer. They go in before the
+         * key stores go out, so that the wait for the value loads is not
+         * a wait for those stores as well. */
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g)   /* the wait, on every path */
+            asm volatile("" : "+v"(val[g]));
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const u32 i = wbase + g * 64 + lane;
+            if (i < tn)
+                s_ovals[(pos2[g >> 1] >> (16 * (g & 1))) & 0xffffu] = val[g];
         }
+        __builtin_amdgcn_sched_barrier(0);   /* no store moves above */
+    }
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c)
+        if (c * 1024 + tid < tn) out_keys[gpos[c]] = k[c];
+    if (!HAS_VAL) return;
+    __syncthreads();                                   /* G */
+    {
+        u32 v[GROUPS];
+#pragma unroll
+        for (int c = 0; c < GROUPS; ++c) v[c] = s_ovals[c * 1024 + tid];
+#pragma unroll
+        for (int c = 0; c < GROUPS; ++c)
+            if (c * 1024 + tid < tn) out_vals[gpos[c]] = v[c];
     }
 }
 
