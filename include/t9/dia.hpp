@@ -1146,7 +1146,8 @@ DIA<ValueType> DIA<ValueType>::ReduceByKey(const KeyExtractor& key_ex,
                              hipMemcpyHostToDevice));
         uint64_t cap = 1024;
         while (cap < 2 * n + 2) cap <<= 1;
-        DeviceBuf tbl(3 * cap * 8), o1(cap * 8), o2(cap * 8), ov(cap * 8);
+        DeviceBuf tbl(t9_reduce128_table_words(cap) * 8);
+        DeviceBuf o1(cap * 8), o2(cap * 8), ov(cap * 8);
         DeviceBuf derr(4), dn(8);
         hipStream_t s = ctx_->stream();
         T9_DIA_TRY(t9_reduce128_init(ctx_->native(), (uint64_t*)tbl.ptr,
@@ -1196,7 +1197,8 @@ DIA<ValueType> DIA<ValueType>::ReduceByKey(const KeyExtractor& key_ex,
                              hipMemcpyHostToDevice));
         uint64_t cap = 1024;
         while (cap < 2 * n + 2) cap <<= 1;
-        DeviceBuf tbl(3 * cap * 8), o1(cap * 8), o2(cap * 8), ov(cap * 8);
+        DeviceBuf tbl(t9_reduce128_table_words(cap) * 8);
+        DeviceBuf o1(cap * 8), o2(cap * 8), ov(cap * 8);
         DeviceBuf derr(4), dn(8);
         hipStream_t s = ctx_->stream();
         T9_DIA_TRY(t9_reduce128_init_op(ctx_->native(), (uint64_t*)tbl.ptr,
@@ -1288,7 +1290,8 @@ TextWordCount(Context& ctx, const std::string& text) {
 
     uint64_t cap = 1024;
     while (cap < 2 * ntok + 2) cap <<= 1;
-    DeviceBuf tbl(3 * cap * 8), o1(cap * 8), o2(cap * 8), ov(cap * 8);
+    DeviceBuf tbl(t9_reduce128_table_words(cap) * 8);
+    DeviceBuf o1(cap * 8), o2(cap * 8), ov(cap * 8);
     T9_DIA_TRY(t9_reduce128_init(nat, (uint64_t*)tbl.ptr, cap, s));
     T9_DIA_TRY(t9_reduce128_build(nat, (const uint64_t*)d1.ptr,
                                   (const uint64_t*)d2.ptr, nullptr, ntok,

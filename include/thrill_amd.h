@@ -243,7 +243,23 @@ int t9_reduce_drain(t9_context* ctx, const uint64_t* d_table,
  * interleaved u64 {k1, k2, sum}, 3*capacity array, capacity a power of
  * two. k1 == ~0 / k2 == ~0 are reserved sentinels (t9_hash2_of remaps
  * them). d_vals == NULL means every pair counts 1.
+ *
+ * Knobs of the plain path, read from the environment on every call:
+ * T9_LDS128_SLOTS picks the per-block LDS filter (>= 4096: 4096, the
+ * default; <= 1024: 1024; otherwise 2048), T9_R128_READFIRST=0 turns the
+ * read-before-CAS probing off (the 1024 filter always runs without it),
+ * T9_REDUCE_GRID fixes the build grid, and T9_R128_STRIDE=4 pads every
+ * slot to 4 u64 {k1, k2, sum, unused}: init, build, drain and lookup then
+ * all address a 4*capacity array. Allocate t9_reduce128_table_words
+ * (capacity) u64 — 3*capacity, or 4*capacity under that knob — not a
+ * literal 3*capacity. The 4-word stride is built for the (4096,
+ * read-first) variant only: with T9_R128_STRIDE=4 and T9_R128_READFIRST=0
+ * or T9_LDS128_SLOTS < 4096, t9_reduce128_build returns T9_EINVAL before
+ * any device call — never a mixed layout.
  * ------------------------------------------------------------------ */
+/* u64 elements of a 128-bit table of `capacity` slots under the current
+ * T9_R128_STRIDE; pure host code. */
+uint64_t t9_reduce128_table_words(uint64_t capacity);
 int t9_reduce128_init(t9_context* ctx, uint64_t* d_table,
                       uint64_t capacity, void* stream);
 int t9_reduce128_build(t9_context* ctx, const uint64_t* d_k1,

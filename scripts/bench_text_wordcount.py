@@ -118,7 +118,8 @@ def stages(nbytes, reps=5, warm=2):
     d_k2 = torch.empty(T, dtype=i64, device="cuda")
     d_slot = torch.empty(T, dtype=i32, device="cuda")
     C = 1 << max(10, (2 * T + 1).bit_length())   # TextWordCount's default
-    d_tbl = torch.empty(3 * C, dtype=i64, device="cuda")
+    d_tbl = torch.empty(nat.reduce128_table_words(C), dtype=i64,
+                        device="cuda")
     d_first = torch.empty(C, dtype=i32, device="cuda")
 
     def timed(name, fn, before=None):

@@ -22,6 +22,10 @@ CHUNKSCAN_UNROLL = 16    # chunks per unrolled trip of k_chunkscan
 CLASSIFY_GRID_CAP = 2048  # blocks of 256: second trip above 524 288 items
 GRID_FOR_CAP = 4096      # t9_reduce.hip grid_for: second trip above 2^20
 RECORDS_GRID_CAP = 16384  # extract / gather block cap
+RED_LDS_PROBES = 4       # probes of a reduce build's per-block LDS filter
+RED_LDS_DEFAULT = 4096   # LDS filter slots when no knob is set
+RED_BUILD_GRID_CAP = 1024  # blocks of 256 of the LDS builds: second trip
+#                            above 262 144 pairs
 
 M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 _K = np.uint64(0x9DDFEA08EB382D69)
@@ -161,3 +165,110 @@ def sort_records(recs):
     recs = np.ascontiguousarray(recs, dtype=np.uint8)
     keys = tuple(recs[:, j] for j in range(recs.shape[1] - 1, -1, -1))
     return recs[np.lexsort(keys)]
+
+
+# ------------------------------------------------- the reduce hash tables
+
+_GOLD = np.uint64(0x9E3779B97F4A7C15)
+
+
+def _salted(salt, keys):
+    keys = u64(keys)
+    return hash128to64(np.full(keys.shape, salt, np.uint64), keys)
+
+
+def reduce_sum(keys, vals):
+    """t9_reduce_* as a set: (sorted unique keys, wrapping u64 sums)."""
+    keys, vals = u64(keys), u64(vals)
+    if len(keys) == 0:
+        return np.empty(0, np.uint64), np.empty(0, np.uint64)
+    order = np.argsort(keys, kind="stable")
+    uk, starts = np.unique(keys[order], return_index=True)
+    return uk, np.add.reduceat(vals[order], starts)
+
+
+def reduce128_sum(k1, k2, vals=None):
+    """t9_reduce128_* as a set: (k1, k2, wrapping sum) triples in
+    lexicographic (k1, k2) order; vals None counts 1 per pair."""
+    k1, k2 = u64(k1), u64(k2)
+    vals = np.ones(len(k1), np.uint64) if vals is None else u64(vals)
+    if len(k1) == 0:
+        return (np.empty(0, np.uint64),) * 3
+    order = np.lexsort((k2, k1))
+    s1, s2 = k1[order], k2[order]
+    first = np.concatenate([[True], (s1[1:] != s1[:-1]) |
+                            (s2[1:] != s2[:-1])])
+    starts = np.flatnonzero(first)
+    return s1[starts], s2[starts], np.add.reduceat(vals[order], starts)
+
+
+def home_slot(keys, salt, cap):
+    """where a key's probe chain starts in a global table of cap slots."""
+    return _salted(salt, keys) & np.uint64(cap - 1)
+
+
+def lds_slot(keys, salt, slots):
+    """where it starts in a build's per-block LDS filter."""
+    return (_salted(salt, keys) >> np.uint64(48)) & np.uint64(slots - 1)
+
+
+def colliding_keys(salt, slots, lds_at, cap, home_at, count):
+    """the first `count` keys i * 0x9E37..15, i in 1..2^22, whose LDS slot
+    is lds_at (of `slots`) and whose home slot is home_at (of `cap`)."""
+    with np.errstate(over="ignore"):
+        cand = np.arange(1, (1 << 22) + 1, dtype=np.uint64) * _GOLD
+    h = _salted(salt, cand)
+    hit = (((h >> np.uint64(48)) & np.uint64(slots - 1)) ==
+           np.uint64(lds_at)) & ((h & np.uint64(cap - 1)) ==
+                                 np.uint64(home_at)) & (cand != M64)
+    found = cand[hit]
+    assert len(found) >= count, (len(found), count)
+    return found[:count]
+
+
+def _chains_unbroken(home, occupied):
+    """every occupied slot is reached from its key's home slot without
+    meeting an empty one (the walk wraps cap-1 -> 0)."""
+    cap = len(occupied)
+    at = np.flatnonzero(occupied)
+    h = home[at].astype(np.int64)
+    dist = (at - h) & (cap - 1)
+    cum = np.concatenate([[0], np.cumsum(np.tile(~occupied, 2))])
+    return np.all(cum[h + dist + 1] - cum[h] == 0)
+
+
+def check_table_u64(raw, cap, salt):
+    """a u64 table (2*(cap+1) words) read back from the device: every key
+    sits in exactly one slot, and its probe chain from the home slot is
+    unbroken. Returns the content as (sorted keys, their value words); the
+    aux slot is not part of it."""
+    raw = u64(raw)
+    assert len(raw) == 2 * (cap + 1)
+    keys, vals = raw[0:2 * cap:2], raw[1:2 * cap:2]
+    occ = keys != M64
+    k = keys[occ]
+    assert len(np.unique(k)) == len(k), "a key occupies two slots"
+    assert _chains_unbroken(home_slot(keys, salt, cap), occ), \
+        "an empty slot between a key's home slot and its slot"
+    order = np.argsort(k)
+    return k[order], vals[occ][order]
+
+
+def check_table_128(raw, cap, salt, stride=3):
+    """the same for a 128-bit table of `stride` words per slot; no slot
+    may hold a k1 without a k2. Returns (k1, k2, value words) in
+    lexicographic order."""
+    t = u64(raw)
+    assert len(t) == stride * cap
+    t = t.reshape(cap, stride)
+    k1, k2, v = t[:, 0], t[:, 1], t[:, 2]
+    occ = k1 != M64
+    assert not np.any(occ & (k2 == M64)), "k1 claimed, k2 left empty"
+    assert not np.any(~occ & (k2 != M64)), "k2 without a k1"
+    pairs = np.stack([k1[occ], k2[occ]], axis=1)
+    assert len(np.unique(pairs, axis=0)) == len(pairs), \
+        "a composite key occupies two slots"
+    assert _chains_unbroken(home_slot(k1, salt, cap), occ), \
+        "an empty slot between a key's home slot and its slot"
+    order = np.lexsort((k2[occ], k1[occ]))
+    return k1[occ][order], k2[occ][order], v[occ][order]

@@ -259,3 +259,160 @@ def test_geometry_constants_match_the_sources():
     m = re.search(r"gcap = gg \? \(u32\)atoi\(gg\) : (\d+);",
                   body_of(rec, "int t9_gather_records("))
     assert m and int(m.group(1)) == R.RECORDS_GRID_CAP
+
+
+# ------------------------------------------------------ reduce hash tables
+
+def sentinel_bearing(rng, n, distinct):
+    """keys from a small set of wide values, the edge keys (sentinel 2^64-1
+    included) mixed in."""
+    pool = np.concatenate([rand_u64(rng, distinct), EDGE])
+    return pool[rng.integers(0, len(pool), n)]
+
+
+@pytest.mark.parametrize("n,distinct", [(1, 1), (257, 5), (20_000, 3000)])
+def test_reduce_sum_matches_oracle(oracle, n, distinct):
+    rng = np.random.default_rng(n)
+    for keys in (rand_u64(rng, distinct)[rng.integers(0, distinct, n)],
+                 sentinel_bearing(rng, n, distinct)):
+        vals = rand_u64(rng, n)                    # sums wrap
+        gk, gv = R.reduce_sum(keys, vals)
+        ek, ev = oracle.reduce_u64(keys, vals)
+        assert np.array_equal(gk, ek) and np.array_equal(gv, ev)
+    ek, ev = R.reduce_sum([], [])
+    assert len(ek) == 0 and len(ev) == 0
+    ek, ev = R.reduce_sum([ONES, 5, ONES], [1 << 63, 7, 1 << 63])
+    assert ek.tolist() == [5, ONES] and ev.tolist() == [7, 0]
+
+
+@pytest.mark.parametrize("n,distinct", [(1, 1), (257, 5), (20_000, 3000)])
+@pytest.mark.parametrize("with_vals", [True, False])
+def test_reduce128_sum_matches_oracle(oracle, n, distinct, with_vals):
+    rng = np.random.default_rng(n + 1)
+    ids = rng.integers(0, distinct, n)
+    # few k1 shared by many k2, so equality has to be on the pair; the
+    # reserved all-ones is no legal k1 or k2
+    k1 = (rand_u64(rng, 1 + distinct // 8) >> np.uint64(1))[ids // 8]
+    k2 = (rand_u64(rng, distinct) >> np.uint64(1))[ids]
+    vals = rand_u64(rng, n) if with_vals else None
+    got = R.reduce128_sum(k1, k2, vals)
+    exp = oracle.reduce128(k1, k2, vals)
+    order = np.lexsort((exp[1], exp[0]))
+    for g, e in zip(got, exp):
+        assert np.array_equal(g, e[order])
+    assert all(len(a) == 0 for a in R.reduce128_sum([], [], None))
+
+
+def test_slot_formulas_and_colliding_keys(oracle):
+    rng = np.random.default_rng(5)
+    keys = np.concatenate([EDGE, rand_u64(rng, 200)])
+    for salt in (0, 1, ONES):
+        h = np.array([oracle.hash128to64(salt, int(k)) for k in keys],
+                     dtype=np.uint64)
+        for cap in (1, 2, 16, 1 << 20):
+            assert np.array_equal(R.home_slot(keys, salt, cap),
+                                  h & np.uint64(cap - 1))
+        for slots in (1024, 2048, 4096, 8192):
+            assert np.array_equal(
+                R.lds_slot(keys, salt, slots),
+                (h >> np.uint64(48)) & np.uint64(slots - 1))
+            c = R.colliding_keys(salt, slots, slots - 2, 16, 14, 16)
+            assert len(np.unique(c)) == 16 and not np.any(c == R.M64)
+            assert np.all(R.lds_slot(c, salt, slots) == slots - 2)
+            assert np.all(R.home_slot(c, salt, 16) == 14)
+
+
+def table_u64(cap, placed, aux=(0, 0)):
+    raw = np.zeros(2 * (cap + 1), np.uint64)
+    raw[0:2 * cap:2] = R.M64
+    for slot, k, v in placed:
+        raw[2 * slot], raw[2 * slot + 1] = k, v
+    raw[2 * cap], raw[2 * cap + 1] = aux
+    return raw
+
+
+def test_check_table_u64_accepts_chains_and_rejects_broken_ones():
+    cap, salt = 16, 1
+    c = R.colliding_keys(salt, 4096, 4094, cap, 14, 4)
+    # a chain from slot 14 across the wrap to slot 1
+    good = table_u64(cap, [(14, c[0], 5), (15, c[1], 6), (0, c[2], 7),
+                           (1, c[3], 0)], aux=(3, 9))
+    k, v = R.check_table_u64(good, cap, salt)
+    order = np.argsort(c)
+    assert np.array_equal(k, c[order])
+    assert np.array_equal(v, np.array([5, 6, 7, 0], np.uint64)[order])
+    # a full table is one unbroken chain
+    full = R.colliding_keys(salt, 4096, 4094, cap, 14, 16)
+    R.check_table_u64(table_u64(cap, [(i, k, 1) for i, k in
+                                      enumerate(full)]), cap, salt)
+    with pytest.raises(AssertionError, match="two slots"):
+        R.check_table_u64(table_u64(cap, [(14, c[0], 5), (15, c[0], 6)]),
+                          cap, salt)
+    with pytest.raises(AssertionError, match="empty slot"):
+        R.check_table_u64(table_u64(cap, [(14, c[0], 5), (0, c[2], 7)]),
+                          cap, salt)
+    with pytest.raises(AssertionError, match="empty slot"):
+        R.check_table_u64(table_u64(cap, [(13, c[0], 5)]), cap, salt)
+
+
+@pytest.mark.parametrize("stride", [3, 4])
+def test_check_table_128_accepts_chains_and_rejects_broken_ones(stride):
+    cap, salt = 16, ONES
+    c = R.colliding_keys(salt, 1024, 1022, cap, 14, 2)
+
+    def table(placed):
+        t = np.full((cap, stride), 0xAB, np.uint64)
+        t[:, 0] = t[:, 1] = R.M64
+        t[:, 2] = 0
+        for slot, a, b, v in placed:
+            t[slot, :3] = a, b, v
+        return t.reshape(-1)
+
+    k1, k2, v = R.check_table_128(
+        table([(14, c[0], 2, 5), (15, c[0], 1, 6), (0, c[1], 1, 7)]),
+        cap, salt, stride)
+    exp = sorted([(int(c[0]), 1, 6), (int(c[0]), 2, 5), (int(c[1]), 1, 7)])
+    assert list(zip(k1.tolist(), k2.tolist(), v.tolist())) == exp
+    with pytest.raises(AssertionError, match="two slots"):
+        R.check_table_128(table([(14, c[0], 2, 5), (15, c[0], 2, 6)]),
+                          cap, salt, stride)
+    with pytest.raises(AssertionError, match="k2 left empty"):
+        R.check_table_128(table([(14, c[0], ONES, 0)]), cap, salt, stride)
+    with pytest.raises(AssertionError, match="empty slot"):
+        R.check_table_128(table([(14, c[0], 2, 5), (0, c[1], 1, 7)]),
+                          cap, salt, stride)
+
+
+def test_reduce_table_geometry_matches_the_sources():
+    red, op = src("t9_reduce.hip"), src("t9_reduce_op.hip")
+    # the LDS filter's start slot: bits 48.. of the salted hash; one such
+    # expression per LDS build kernel
+    assert red.count("u32 ls = (u32)(h >> 48) & (T9_LDS_SLOTS - 1);") == 1
+    assert red.count("u32 ls = (u32)(h >> 48) & (SLOTS - 1);") == 1
+    assert op.count("u32 ls = (u32)(h >> 48) & (SLOTS - 1);") == 2
+    # its probe count
+    assert red.count("for (int p = 0; p < 4; ++p)") == 2
+    assert op.count("for (int p = 0; p < 4; ++p)") == 2
+    assert R.RED_LDS_PROBES == 4
+    # the home slot: the low bits of the same hash
+    assert "u64 slot = h & (cap - 1);" in red
+    assert "u64 slot = h & (cap - 1);" in op
+    assert "u64 slot = t9_hash128to64(salt, k1) & (cap - 1);" in red
+    assert "u64 slot = t9_hash128to64(salt, k1) & (cap - 1);" in op
+    # default filter size and the grid clamp of the four build entry points
+    for text, fn in ((red, "t9_reduce_build"), (red, "t9_reduce128_build"),
+                     (op, "t9_reduce_build_op"),
+                     (op, "t9_reduce128_build_op")):
+        m = re.search(r"const int slots = se \? atoi\(se\) : (\d+);",
+                      body_of(text, "int " + fn + "("))
+        assert m and int(m.group(1)) == R.RED_LDS_DEFAULT == 4096, fn
+    for fn in ("t9_reduce_build", "t9_reduce128_build"):
+        m = re.search(r"if \(!ge && grid > (\d+)\) grid = (\d+);",
+                      body_of(red, "int " + fn + "("))
+        assert m and int(m.group(1)) == int(m.group(2)) == \
+            R.RED_BUILD_GRID_CAP == 1024, fn
+    m = re.search(r"\*grid = g > (\d+) \? (\d+) : g;",
+                  body_of(op, "bool env_grid("))
+    assert m and int(m.group(1)) == int(m.group(2)) == R.RED_BUILD_GRID_CAP
+    # the wave pre-combine matches lanes on 11 bits of the LDS slot
+    assert "for (int b = 0; b < 11; ++b)" in red

@@ -3,21 +3,26 @@ primitives (classify, partition, bucket mappings, reduce-by-index, merge,
 gather, extract, group index): every invalid call below is refused with
 T9_EINVAL, and every empty merge answered with T9_OK, before any device
 call — so each returns without a GPU. The workspace queries are pure host
-code."""
+code. So are the 128-bit reduce table's sizing query and the refusal of a
+4-word slot stride by a build variant that has none."""
 import ctypes
 import os
+import re
 
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T9_SO = os.path.join(REPO, "thrill_amd", "libt9.so")
+HEADER = os.path.join(REPO, "include", "thrill_amd.h")
 
 SYMBOLS = ["t9_classify_u64", "t9_classify_rec", "t9_partition_idx",
            "t9_partition_idx_workspace", "t9_hash_bucket", "t9_bucket_mod",
            "t9_index_bucket", "t9_reduce_by_index", "t9_merge_u64",
            "t9_merge_records", "t9_gather_records", "t9_extract_key64",
            "t9_extract_key64_le", "t9_group_index",
-           "t9_group_index_workspace"]
+           "t9_group_index_workspace", "t9_reduce128_table_words",
+           "t9_reduce128_init", "t9_reduce128_build", "t9_reduce128_drain",
+           "t9_reduce128_lookup"]
 
 OK, EINVAL = 0, -22
 # never dereferenced: every call below must end during validation
@@ -185,3 +190,59 @@ def test_workspace_queries_are_monotone_and_nonzero(t9lib, query, tile,
     assert sizes == sorted(sizes), sizes
     for n, b in zip(ns, sizes):
         assert b >= row_bytes * ((n + tile - 1) // tile), (n, b)
+
+
+# ------------------------------------------------ 128-bit table slot stride
+
+def test_reduce128_symbols_exported_with_matching_arity(t9lib):
+    from thrill_amd.native import _SIGS
+    with open(HEADER) as f:
+        text = f.read()
+    for s in SYMBOLS[-5:]:
+        assert s.startswith("t9_reduce128_")
+        assert hasattr(t9lib, s), f"libt9.so missing symbol {s}"
+        m = re.search(r"^(?:int|uint64_t)\s+" + s + r"\s*\(([^)]*)\)", text,
+                      re.M)
+        assert m, f"{s} not declared in thrill_amd.h"
+        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        assert len(_SIGS[s][1]) == nargs, (s, len(_SIGS[s][1]), nargs)
+
+
+def build128(lib, n=16, vals=FAKE):
+    return lib.t9_reduce128_build(None, FAKE, FAKE, vals, n, FAKE, 1024, 0,
+                                  FAKE, None)
+
+
+@pytest.mark.parametrize("env", [
+    {"T9_R128_READFIRST": "0"},
+    {"T9_LDS128_SLOTS": "1024"},
+    {"T9_LDS128_SLOTS": "2048"},
+    {"T9_LDS128_SLOTS": "4095"},
+    {"T9_LDS128_SLOTS": "2048", "T9_R128_READFIRST": "0"}],
+    ids=lambda e: ",".join(f"{k[3:]}={v}" for k, v in e.items()))
+def test_stride4_without_a_stride4_build_is_refused(t9lib, monkeypatch,
+                                                    env):
+    # init, drain and lookup would address 4-word slots; the selected build
+    # variant exists with 3-word slots only: T9_EINVAL before any device
+    # call, whatever n and vals are
+    for k in ("T9_R128_READFIRST", "T9_LDS128_SLOTS"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("T9_R128_STRIDE", "4")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    assert build128(t9lib) == EINVAL
+    assert build128(t9lib, vals=None) == EINVAL
+    assert build128(t9lib, n=0) == EINVAL
+
+
+def test_reduce128_table_words_follows_the_stride_knob(t9lib, monkeypatch):
+    f = t9lib.t9_reduce128_table_words
+    caps = [1, 2, 16, 1024, 1 << 31]
+    monkeypatch.delenv("T9_R128_STRIDE", raising=False)
+    assert [f(c) for c in caps] == [3 * c for c in caps]
+    monkeypatch.setenv("T9_R128_STRIDE", "4")
+    assert [f(c) for c in caps] == [4 * c for c in caps]
+    # any other value is the packed layout, as in init/build/drain/lookup
+    for other in ("3", "0", "8", ""):
+        monkeypatch.setenv("T9_R128_STRIDE", other)
+        assert [f(c) for c in caps] == [3 * c for c in caps]

@@ -799,11 +799,16 @@ int t9_reduce_build(t9_context* ctx, const u64* d_keys, const u64* d_vals,
 
 /* slot stride: 3 u64s packed (default; table = 3*capacity u64s) or 4
    (T9_R128_STRIDE=4: 32-B line-aligned slots, table = 4*capacity u64s —
-   the CALLER must allocate accordingly; A/B knob) */
+   the CALLER must allocate accordingly, t9_reduce128_table_words says
+   how much; A/B knob) */
 static u32 r128_stride() {
     const char* e = getenv("T9_R128_STRIDE");
     return (e && atoi(e) == 4) ? 4u : 3u;
 }
+
+/* u64 words of a 128-bit table under the current stride knob; pure host
+   code */
+u64 t9_reduce128_table_words(u64 cap) { return (u64)r128_stride() * cap; }
 
 int t9_reduce128_init(t9_context* ctx, u64* d_table, u64 cap,
                       void* stream) {
@@ -820,12 +825,6 @@ int t9_reduce128_build(t9_context* ctx, const u64* d_k1, const u64* d_k2,
                        u64 salt, u32* d_error, void* stream) {
     (void)ctx;
     if (!d_table || !d_error || !is_pow2(cap)) return T9_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(d_error, 0, 4, s));
-    if (n == 0) return T9_OK;
-    if (!d_k1 || !d_k2) return T9_EINVAL;
-    /* d_vals may be NULL: every pair counts 1 (the word_count PreOp
-     * emits (word, 1) — word_count.hpp:43-45) */
     /* measured at 2^29 Zipf(1.1) tokens, 10M vocab: 4096 (1 block/CU,
      * 96 KB LDS) 34.6 ms beats 2048 (36.1) and 1024 (45.5) — hot-key
      * coverage over occupancy, as in the u64 table */
@@ -841,6 +840,17 @@ int t9_reduce128_build(t9_context* ctx, const u64* d_k1, const u64* d_k2,
     const char* rf = getenv("T9_R128_READFIRST");
     const bool readfirst = !(rf && rf[0] == '0');
     const bool s4 = r128_stride() == 4;
+    /* the 4-u64 slot stride is instantiated for (4096 slots, readfirst)
+     * only; init, drain and lookup follow the knob, so any other build
+     * would run a 3-word-stride kernel on a 4-word-stride table. Refuse
+     * before any device call — never a mixed layout. */
+    if (s4 && !(slots >= 4096 && readfirst)) return T9_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_error, 0, 4, s));
+    if (n == 0) return T9_OK;
+    if (!d_k1 || !d_k2) return T9_EINVAL;
+    /* d_vals may be NULL: every pair counts 1 (the word_count PreOp
+     * emits (word, 1) — word_count.hpp:43-45) */
     T9_PERF_WRAP(
         s, "reduce_build",
         if (slots >= 4096 && readfirst && s4)

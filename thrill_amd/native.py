@@ -73,6 +73,7 @@ _SIGS = {
     "t9_reduce_init": (i32, [vp, vp, u64, vp]),
     "t9_reduce_build": (i32, [vp, vp, vp, u64, vp, u64, u64, vp, vp]),
     "t9_reduce_drain": (i32, [vp, vp, u64, vp, vp, vp, vp]),
+    "t9_reduce128_table_words": (u64, [u64]),
     "t9_reduce128_init": (i32, [vp, vp, u64, vp]),
     "t9_reduce128_build": (i32, [vp, vp, vp, vp, u64, vp, u64, u64, vp,
                                  vp]),
@@ -193,6 +194,12 @@ class Native:
     def ws(self, name, *args):
         """workspace byte queries (no ctx argument)."""
         return getattr(self._lib, f"t9_{name}_workspace")(*args)
+
+    def reduce128_table_words(self, capacity):
+        """u64 elements of a 128-bit reduce table: 3 * capacity, or
+        4 * capacity under T9_R128_STRIDE=4; no ctx argument, pure host
+        code."""
+        return self._lib.t9_reduce128_table_words(capacity)
 
     def scan_geometry(self):
         """(tile elements, tile totals per block of the middle pass) of

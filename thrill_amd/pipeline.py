@@ -168,9 +168,10 @@ class WordCount:
                                     device="cuda")
             self.d_k2 = torch.empty(self.n_local, dtype=torch.int64,
                                     device="cuda")
-            # interleaved (k1, k2, sum) table: u64[3*cap]
-            self.d_tbl = torch.empty(3 * cap, dtype=torch.int64,
-                                     device="cuda")
+            # interleaved (k1, k2, sum) table: u64[3*cap], u64[4*cap]
+            # under T9_R128_STRIDE=4
+            self.d_tbl = torch.empty(self.nat.reduce128_table_words(cap),
+                                     dtype=torch.int64, device="cuda")
             self.d_ok2 = torch.empty(cap, dtype=torch.int64, device="cuda")
         else:
             # interleaved (key, sum) table: u64[2*(cap+1)]
@@ -774,7 +775,8 @@ class TextWordCount:
         if capacity is None:
             capacity = 1 << max(10, (2 * ntok + 1).bit_length())
         cap = int(capacity)
-        d_tbl = torch.empty(3 * cap, dtype=i64, device="cuda")
+        d_tbl = torch.empty(nat.reduce128_table_words(cap), dtype=i64,
+                            device="cuda")
         d_o1 = torch.empty(cap, dtype=i64, device="cuda")
         d_o2 = torch.empty(cap, dtype=i64, device="cuda")
         d_ov = torch.empty(cap, dtype=i64, device="cuda")
