@@ -139,6 +139,18 @@ int t9_sort_last_schedule(const t9_context* ctx);
  * sorted keys (every other flow). The sorted output is the same. */
 int t9_sort_last_tiecount(const t9_context* ctx);
 
+/* Whether the last t9_sort_records / t9_sort_records_keyle call on this
+ * context ran the fused sub-bucket sort + payload gather kernel (100-byte
+ * records on the two-level 9-bit MSB flow, every sub-bucket within 1024
+ * records, event timing off, T9_SORT_OVERLAP unset): 1 = it produced the
+ * output; 2 = it started, but equal 8-byte prefixes it could not settle in
+ * the block made the tie path and a full gather redo the output; 0 = the
+ * sort and the gather ran as separate kernels. The fused kernel is the
+ * default (measured faster on MI355X);
+ * T9_SORT_FUSED_GATHER=0 restores the separate kernels. The sorted output is
+ * the same. */
+int t9_sort_last_fused(const t9_context* ctx);
+
 /* ------------------------------------------------------------------ *
  * Classification + partition — replaces TransmitItems' tree-descent loop
  * (thrill/api/sort.hpp:434-535). bucket(item i) = #{ j : (splitter_key[j],

@@ -210,6 +210,86 @@ __device__ __forceinline__ void t9_w16_row_load(const u64* lc, u32 row,
     }
 }
 
+/* the blocksort of k_wave16_sort_sub (in-lane network + merge rounds) as a
+ * function, for k_wave16_sort_gather; k_wave16_sort_sub keeps its own
+ * inline copy so that its code stays exactly what was measured. Lane
+ * `lane` enters with its 16 contiguous elements in c[] and leaves with
+ * elements lane * 16 .. + 15 of the sorted block. lc is scratch (every
+ * round starts with a barrier of its own). */
+template <int E, int ROUNDS>
+__device__ __forceinline__ void t9_w16_blocksort(u64* lc, u32 lane,
+                                                 u64 (&c)[E]) {
+    const u32 e0 = lane * E;
+    /* in-register bitonic sort of the lane's 16 elements (pure VALU) */
+#pragma unroll
+    for (int lk = 1; lk <= 4; ++lk) {
+        const int k = 1 << lk;
+#pragma unroll
+        for (int lj = lk - 1; lj >= 0; --lj) {
+            const int j = 1 << lj;
+#pragma unroll
+            for (int r = 0; r < E; ++r) {
+                const int q = r ^ j;
+                if (q > r) {
+                    const bool asc = (r & k) == 0;
+                    if ((c[r] > c[q]) == asc) {
+                        u64 tc = c[r]; c[r] = c[q]; c[q] = tc;
+                    }
+                }
+            }
+        }
+    }
+
+    /* 6 merge rounds: sorted runs of L pairwise -> 2L via merge-path.
+     * Composites are unique, so `<=` against the B run is a stable merge
+     * (A-run elements precede equal... equality cannot occur). */
+#pragma unroll
+    for (int lm = 0; lm < ROUNDS; ++lm) {
+        const u32 L = (u32)E << lm;
+        __syncthreads();
+        t9_w16_row_store(lc, lane, c);
+        __syncthreads();
+        const u32 pairbase = e0 & ~(2 * L - 1);
+        const u32 d = e0 - pairbase;          /* my first output diagonal */
+        const u32 ab = pairbase, bb = pairbase + L;   /* run A, run B */
+        u32 lo = (d > L) ? d - L : 0;
+        u32 hi = (d < L) ? d : L;
+        while (lo < hi) {
+            const u32 m = (lo + hi) >> 1;
+            if (lc[t9_w16_phys(ab + m)] <= lc[t9_w16_phys(bb + d - m - 1)])
+                lo = m + 1;
+            else hi = m;
+        }
+        /* both run heads live in registers; each step emits the
+         * smaller one and reads only that side's successor. An
+         * exhausted run reads as ~0, above every live composite
+         * (60 bits) and equal to the pads, which never leave. */
+        u32 ia = ab + lo, ib = bb + (d - lo);
+        const u32 ea = bb, eb = bb + L;
+        /* reads are unconditional at a clamped index and the value is
+         * selected afterwards: no divergent branch per step */
+        const u64 a0 = lc[t9_w16_phys(ia < ea ? ia : ab)];
+        const u64 b0 = lc[t9_w16_phys(ib < eb ? ib : ab)];
+        u64 a = (ia < ea) ? a0 : ~0ull;
+        u64 b = (ib < eb) ? b0 : ~0ull;
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+            const bool ta = a <= b;
+            c[r] = ta ? a : b;
+            if (r + 1 < E) {
+                ia += ta ? 1u : 0u;
+                ib += ta ? 0u : 1u;
+                const u32 nx = ta ? ia : ib;
+                const bool in = nx < (ta ? ea : eb);
+                const u64 ld = lc[t9_w16_phys(in ? nx : ab)];
+                const u64 nv = in ? ld : ~0ull;
+                a = ta ? nv : a;
+                b = ta ? b : nv;
+            }
+        }
+    }
+}
+
 /* REC (record sort only; needs HAS_VAL): the block also counts its
  * equal-key neighbours into *ntied — the number k_count_tied would find in
  * this sub-bucket; ties cannot cross sub-buckets, whose top key bits
@@ -395,6 +475,225 @@ __global__ __launch_bounds__(BLOCK, 2) void k_wave16_sort_sub(
         for (int r = 0; r < E; ++r) {
             const u32 p = lane + (u32)BLOCK * r;
             if (p < ns) kb[p] = high16 | (lc[t9_w16_phys(p)] >> 12);
+        }
+    }
+}
+
+/* ------------------------------------------------------------------ *
+ * k_wave16_sort_gather: the record sort's sub-bucket sort and payload
+ * gather in one kernel (1024 tier, 100-byte records). The block runs the
+ * k_wave16_sort_sub<1024, 64, true, true> body on its sub-bucket and then
+ * copies that sub-bucket's records, out[gbase + i] = rin[idx[i]], so the
+ * sort's latency chain sits inside the gather's slot-time instead of
+ * ahead of it and the sorted index is never read back from memory.
+ *
+ * Phases and who owns lc:
+ *   1 load, blocksort, tie count    lc = composites (as the plain kernel)
+ *   2 short ties settled (TIES)     lc = composites, position fields of
+ *                                   equal-key runs of <= T9_FUSED_RUNMAX
+ *                                   swapped into full-record order
+ *   3 values and keys written back  lc = composites (read only)
+ *   4 gather                        lc = the ns sorted record indices, u32
+ * Tie protocol (invariants of k_wave16_sort_sub kept): d_idx is always
+ * written; the keys of a sub-bucket with ANY equal neighbours are written,
+ * settled or not, so a later k_tie_flags never meets equal keys in an
+ * unsorted sub-bucket. Only the ties the block could not settle go to
+ * *ntied (runs longer than T9_FUSED_RUNMAX, the all-equal shortcut); such
+ * a block skips its gather, and every block skips it once *ntied is
+ * non-zero, as the output is then redone by the tie path and the full
+ * gather. *ntied == 0 after the kernel therefore means: out is complete.
+ * ------------------------------------------------------------------ */
+#define T9_FUSED_RUNMAX 8
+
+/* strict bytewise less on bytes 8..99 of two 100-byte records */
+__device__ __forceinline__ bool t9_rec100_tail_less(
+    const u32* __restrict__ rin, u32 ra, u32 rb) {
+    const u32* a = rin + (u64)ra * 25;
+    const u32* b = rin + (u64)rb * 25;
+#pragma unroll 1
+    for (int w = 2; w < 25; ++w) {
+        const u32 x = __builtin_bswap32(a[w]), y = __builtin_bswap32(b[w]);
+        if (x != y) return x < y;
+    }
+    return false;
+}
+
+template <int D, bool TIES>
+__global__ __launch_bounds__(64, 2) void k_wave16_sort_gather(
+    u64* __restrict__ keys, u32* __restrict__ vals,
+    const u32* __restrict__ sub_start, const u32* __restrict__ sub_n,
+    u32* ntied, const u32* __restrict__ rin, u32* __restrict__ rout) {
+    constexpr int NSORT = 1024, BLOCK = 64, E = 16, ROUNDS = 6, RW = 25;
+    __shared__ __attribute__((aligned(16))) u64 lc[NSORT];
+    __shared__ u32 s_differ;
+    __shared__ u32 s_ntie;
+    __shared__ u32 s_settled;
+
+    const u32 sb = blockIdx.x;
+    const u32 ns = sub_n[sb];
+    if (ns == 0 || ns > (u32)NSORT) return;
+    const u32 gbase = sub_start[sb];
+    const u32 lane = threadIdx.x;
+    const u32 e0 = lane * E;
+    u32* const ob = rout + (u64)gbase * RW;
+
+    if (ns == 1) {
+        /* nothing to sort; the single record still has to be copied */
+        if (__hip_atomic_load(ntied, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        if (lane < (u32)RW) ob[lane] = rin[(u64)vals[gbase] * RW + lane];
+        return;
+    }
+
+    if (lane == 0) { s_differ = 0; s_ntie = 0; s_settled = 0; }
+    __syncthreads();
+
+    const u64 mask48 = 0x0000FFFFFFFFFFFFull;
+    const u64 high16 = keys[gbase] & ~mask48;
+    const u64 ref48 = keys[gbase] & mask48;
+
+    u64 c[E];
+    u32 differ = 0;
+    u64* const kb = keys + gbase;
+    u32* const vb = vals + gbase;
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        u64 cc = ~0ull;
+        if (p < ns) {
+            const u64 k = kb[p];
+            cc = ((k & mask48) << 12) | (u64)p;
+            differ |= ((k & mask48) != ref48);
+        }
+        lc[t9_w16_phys(p)] = cc;
+    }
+    if (differ) s_differ = 1;
+    __syncthreads();
+    if (!s_differ) {
+        /* all keys equal: ns - 1 ties for the tie path, no gather */
+        if (lane == 0) atomicAdd(ntied, ns - 1);
+        return;
+    }
+    t9_w16_row_load(lc, lane, c);
+
+    t9_w16_blocksort<E, ROUNDS>(lc, lane, c);
+
+    __syncthreads();
+    t9_w16_row_store(lc, lane, c);
+    __syncthreads();
+    {
+        const u64 nxt = (e0 + E < (u32)NSORT) ? lc[t9_w16_phys(e0 + E)]
+                                              : ~0ull;
+        u32 cnt = 0;
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+            const u64 hi = (r + 1 < E) ? c[r + 1] : nxt;
+            cnt += (e0 + r + 1 < ns) && ((c[r] >> 12) == (hi >> 12));
+        }
+        if (cnt) atomicAdd(&s_ntie, cnt);
+    }
+    __syncthreads();
+    const u32 nt = s_ntie;   /* equal neighbours, settled or not */
+    if (TIES && nt) {
+        /* each lane settles the runs that START among its 16 elements: a
+         * run of <= T9_FUSED_RUNMAX equal keys is insertion-sorted by the
+         * rest of the record (strict less, so true duplicates keep input
+         * order) by swapping the 12-bit position fields only. Runs are
+         * disjoint, and other lanes' swaps never touch the key bits that
+         * the scans below compare. vb still holds the unsorted indices. */
+        u32 settled = 0;
+#pragma unroll 1
+        for (u32 e = e0; e < e0 + E && e + 1 < ns; ++e) {
+            const u64 key = lc[t9_w16_phys(e)] >> 12;
+            if ((lc[t9_w16_phys(e + 1)] >> 12) != key) continue;
+            if (e > 0 && (lc[t9_w16_phys(e - 1)] >> 12) == key) continue;
+            u32 len = 2;
+            while (len <= T9_FUSED_RUNMAX && e + len < ns &&
+                   (lc[t9_w16_phys(e + len)] >> 12) == key)
+                ++len;
+            if (len > T9_FUSED_RUNMAX) continue;   /* left to the tie path */
+            for (u32 i = 1; i < len; ++i)
+                for (u32 j = i; j > 0; --j) {
+                    const u32 hi_at = t9_w16_phys(e + j);
+                    const u32 lo_at = t9_w16_phys(e + j - 1);
+                    const u64 ch = lc[hi_at], cl = lc[lo_at];
+                    const u32 ph = (u32)ch & 0xFFFu, pl = (u32)cl & 0xFFFu;
+                    if (!t9_rec100_tail_less(rin, vb[ph], vb[pl])) break;
+                    lc[hi_at] = (ch & ~0xFFFull) | pl;
+                    lc[lo_at] = (cl & ~0xFFFull) | ph;
+                }
+            settled += len - 1;
+        }
+        if (settled) atomicAdd(&s_settled, settled);
+    }
+    __syncthreads();
+    /* the sorted record indices, re-gathered from the embedded original
+     * positions; all reads complete before any lane writes (barrier) */
+    u32 v[E];
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        if (p < ns) v[r] = vb[(u32)lc[t9_w16_phys(p)] & 0xFFFu];
+    }
+    __syncthreads();
+    const u32 unsettled = nt - s_settled;
+    if (lane == 0 && unsettled) atomicAdd(ntied, unsettled);
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        if (p < ns) vb[p] = v[r];
+    }
+    if (nt) {
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+            const u32 p = lane + (u32)BLOCK * r;
+            if (p < ns) kb[p] = high16 | (lc[t9_w16_phys(p)] >> 12);
+        }
+    }
+    if (unsettled) return;   /* the tie path redoes the output */
+
+    /* ---- gather phase: lc becomes the index buffer ---- */
+    __syncthreads();
+    u32* const li = (u32*)lc;
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        if (p < ns) li[p] = v[r];
+    }
+    __syncthreads();
+    if (__hip_atomic_load(ntied, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        return;
+    /* word-wise, consecutive lanes on consecutive output words (the
+     * access shape of k_gather_records_span), D independent loads in
+     * flight per lane */
+    const u32 W = ns * RW;
+    for (u32 g0 = lane; g0 < W; g0 += (u32)BLOCK * D) {
+        u32 x[D];
+        if (g0 - lane + (u32)BLOCK * D <= W) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const u32 g = g0 + (u32)BLOCK * j;
+                const u32 rec = g / (u32)RW;
+                x[j] = rin[(u64)li[rec] * RW + (g - rec * RW)];
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) ob[g0 + (u32)BLOCK * j] = x[j];
+        }
+        else {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const u32 g = g0 + (u32)BLOCK * j;
+                if (g < W) {
+                    const u32 rec = g / (u32)RW;
+                    x[j] = rin[(u64)li[rec] * RW + (g - rec * RW)];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const u32 g = g0 + (u32)BLOCK * j;
+                if (g < W) ob[g] = x[j];
+            }
         }
     }
 }

@@ -59,6 +59,7 @@ struct t9_context {
     int ov_ready;
     int last_schedule;   /* t9_sort_last_schedule */
     int last_tiecount;   /* t9_sort_last_tiecount */
+    int last_fused;      /* t9_sort_last_fused */
 };
 
 /* record-sort request riding along the pair sort: when the two-level
@@ -66,12 +67,16 @@ struct t9_context {
  * chunk on the context's internal stream while later sub-buckets are
  * still being sorted; the sub-sort's own tie counter (the d_ntied passed
  * next to this request) is the gathers' abort flag. chunks stays 0 when
- * the serial schedule ran — then the caller gathers itself. */
+ * the serial schedule ran — then the caller gathers itself. fused = 1:
+ * the sub-bucket sort gathered every sub-bucket itself
+ * (k_wave16_sort_gather), and out is complete iff the tie counter stayed
+ * zero. */
 struct t9_overlap_req {
     const u8* recs;
     u8* out;
     u32 rec_words;
     u32 chunks;   /* out: non-empty chunks gathered on the internal stream */
+    u32 fused;    /* out: 1 = the fused sort + gather kernel ran */
 };
 
 /* splitmix64 random access — must match oracle/t9_oracle.cpp splitmix64_at */

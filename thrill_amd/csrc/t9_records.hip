@@ -855,14 +855,18 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
     bool fused = fe && atoi(fe) && n >= (1ull << 14) &&
                  (rec_size == 100 || rec_size == 128);
     int rc;
-    t9_overlap_req ov = { nullptr, nullptr, 0, 0 };
+    t9_overlap_req ov = { nullptr, nullptr, 0, 0, 0 };
     /* 1: the sub-bucket sort counted the ties into d_ntied itself; then
      * d_keys is sorted only inside sub-buckets that hold a tie (see
      * k_wave16_sort_sub), which is all its readers below need: k_tie_flags
      * compares neighbours (none equal in an unwritten sub-bucket, whose
      * keys are distinct) and the tied-prefix gather reads tied positions */
     int tie_counted = 0;
-    if (ctx) { ctx->last_schedule = 0; ctx->last_tiecount = 0; }
+    if (ctx) {
+        ctx->last_schedule = 0;
+        ctx->last_tiecount = 0;
+        ctx->last_fused = 0;
+    }
     if (eh && !fused) {
         u32* hist = t9i_msb_pass1_hist(pair_ws, n);
         const u64 B = t9_ceil_div(n, 8192);
@@ -886,7 +890,8 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
         T9_LAUNCH_CHECK();
         /* 100-byte records through the default span gather may be
          * gathered chunk by chunk while the sub-bucket sort is still
-         * running (sort_msb_impl decides; ov.chunks says what ran) */
+         * running, or by the sub-bucket sort itself (sort_msb_impl decides;
+         * ov.chunks and ov.fused say what ran) */
         const char* gv = getenv("T9_GATHER_VARIANT");
         const bool may_overlap = rw == 25 && ctx && !(gv && atoi(gv) != 3);
         if (may_overlap) {
@@ -929,6 +934,13 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
          * grows, so none saw the abort flag) and d_out is complete. With
          * ties the speculative writes into d_out are finished (join) and
          * the tie machinery + full gather below redo it. */
+        if (!ntied) return T9_OK;
+    }
+    if (ov.fused) {
+        /* k_wave16_sort_gather: with no tie left for the tie path every
+         * block gathered its sub-bucket and d_out is complete; otherwise
+         * some blocks skipped theirs and the output is redone below */
+        ctx->last_fused = ntied ? 2 : 1;
         if (!ntied) return T9_OK;
     }
 

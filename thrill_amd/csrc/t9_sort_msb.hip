@@ -1073,6 +1073,28 @@ static u32 overlap_chunks() {
     return (u32)k;
 }
 
+/* Fused sub-bucket sort + payload gather (k_wave16_sort_gather,
+ * t9_bitonic.h). On by default (-0.5 ms
+ * per 10 GiB step); T9_SORT_FUSED_GATHER=0 restores the separate sort and
+ * gather kernels for A/B and parity. T9_FUSED_D (loads in flight per
+ * lane in the gather phase) and T9_FUSED_TIES (settle short tie runs in the
+ * block) are build-time, for the A/B builds of that round. */
+#ifndef T9_FUSED_D
+#define T9_FUSED_D 16
+#endif
+#ifndef T9_FUSED_TIES
+#define T9_FUSED_TIES 1
+#endif
+#ifndef T9_FUSED_DEFAULT
+#define T9_FUSED_DEFAULT 1
+#endif
+
+static bool t9i_fused_gather() {
+    const char* e = getenv("T9_SORT_FUSED_GATHER");
+    if (!e || e[0] == '\0') return T9_FUSED_DEFAULT != 0;
+    return e[0] != '0';
+}
+
 /* out[0..1] = info[0..1] (k_subinfo's max and oversize count), out[1 + c]
  * = first record of chunk c (c = 1..K-1): one read-back fetches all.
  * sub_start is a running exclusive sum over the sub-buckets (k_seg_scan9:
@@ -1227,6 +1249,24 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                         s, ctx->ov_ev[T9_OVERLAP_MAXK], 0));
                     ov->chunks = done;
                     return T9_OK;
+                }
+            }
+            /* fused sort + gather (k_wave16_sort_gather): wherever the
+             * chunked schedule could have run, was not asked for, and the
+             * 1024 tier holds every sub-bucket. Event timing keeps the two
+             * stand-alone kernels so that their classes stay measurable. */
+            if constexpr (HAS_VAL) {
+                if (tcount && ov && ctx && !t9perf_on() && ov->recs &&
+                    ov->rec_words == 25 && overlap_chunks() == 0 &&
+                    maxsub <= 1024 && t9i_fused_gather()) {
+                    hipLaunchKernelGGL(
+                        (k_wave16_sort_gather<T9_FUSED_D, T9_FUSED_TIES != 0>),
+                        dim3((u32)NSUB9), dim3(64), 0, s, d_keys, d_vals,
+                        w.sub_start, w.sub_n, tcount, (const u32*)ov->recs,
+                        (u32*)ov->out);
+                    T9_LAUNCH_CHECK();
+                    ov->fused = 1;
+                    return T9_OK;   /* tcount implies novr9 == 0 */
                 }
             }
             T9_PERF_WRAP(
