@@ -512,6 +512,55 @@ int t9_fold_u64(t9_context* ctx, const uint64_t* d_in, uint64_t n,
                 uint32_t stride_words, int op, int vtype, uint64_t* d_out,
                 void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * InnerJoin — the matching half of the reference's sort-based join
+ * (thrill/api/inner_join.hpp:213-287): the list of all index pairs (i, j)
+ * with lkeys[i] == rkeys[j], ordered by key ascending as unsigned 64-bit,
+ * then by i ascending, then by j ascending. Every u64 value is a legal key
+ * (no sentinel); the inputs are not modified; the result is a deterministic
+ * function of the inputs (no atomics, no hash table). Payloads are not the
+ * join's business: materialise rows with t9_gather_records on the two
+ * index arrays.
+ *
+ * t9_join_count sorts (key, index) pairs of both sides stably, finds every
+ * left element's range of equal right keys, scans the range lengths, leaves
+ * all of that in d_workspace, synchronises the stream and returns the
+ * number of result pairs through the HOST pointer `total` (one word read
+ * back). t9_join_emit writes positions [0, min(n_out, total)) of the result
+ * and touches nothing else: a short buffer receives a prefix. It needs the
+ * n_left / n_right / d_workspace of the count, launches on `stream` without
+ * synchronising, and may be called more than once on one workspace. Work is
+ * divided by output position, so one key that is hot on both sides costs
+ * per row what unique keys cost (DESIGN.md "Join").
+ *
+ * t9_join_geometry: left keys per block of the matching kernel, output
+ * positions per block of the emit kernel, and the most right keys a matching
+ * block stages in LDS (a longer candidate slice is searched in global
+ * memory). t9_join_workspace(n_left, n_right) bytes, monotone in both,
+ * include the nested sort and scan workspaces; d_workspace must be 16-byte
+ * aligned (hipMalloc memory is) and need not be zeroed. Both are pure host
+ * code. Two A/B knobs, read on every call, change speed only:
+ * T9_JOIN_GALLOP=0 (plain binary search for the upper bound) and
+ * T9_JOIN_EMIT_V4=0 (4-byte instead of 16-byte stores; also what runs when
+ * an output pointer is not 16-byte aligned).
+ *
+ * Validation comes before any device call; each of these is T9_EINVAL:
+ * n_left or n_right >= 2^32, NULL total, NULL keys of a non-empty side,
+ * NULL or misaligned d_workspace, a NULL output with n_out > 0, 2^31 output
+ * tiles or more. An empty side gives *total = 0 and T9_OK without a launch
+ * (the reference returns early there too), and t9_join_emit with an empty
+ * side or n_out == 0 is T9_OK without a launch.
+ * ------------------------------------------------------------------ */
+void t9_join_geometry(uint32_t* left_tile, uint32_t* out_tile,
+                      uint32_t* stage_keys);
+uint64_t t9_join_workspace(uint64_t n_left, uint64_t n_right);
+int t9_join_count(t9_context* ctx, const uint64_t* d_lkeys, uint64_t n_left,
+                  const uint64_t* d_rkeys, uint64_t n_right,
+                  uint64_t* total, void* d_workspace, void* stream);
+int t9_join_emit(t9_context* ctx, uint64_t n_left, uint64_t n_right,
+                 const void* d_workspace, uint64_t n_out,
+                 uint32_t* d_out_left, uint32_t* d_out_right, void* stream);
+
 /* GroupByKey support (SURVEY.md §8f item 3 — thrill/api/group_by_key.hpp
  * is sort-based): the group index of a key-sorted array. d_unique[g] /
  * d_offsets[g] (ascending run starts) for g in [0, *d_count); d_count is
@@ -549,7 +598,8 @@ int t9_zipf_tokens(t9_context* ctx, uint64_t* d_out, const double* d_cdf,
  * bench harness's roofline measurement. Classes: "pair_scatter",
  * "keys_scatter", "hist_pairs", "hist_keys", "extract", "gather",
  * "reduce_build_op", "scan" (one t9_scan_* or t9_fold_u64 call, all its
- * launches) and "scan_pass2" (the middle pass of a scan alone).
+ * launches), "scan_pass2" (the middle pass of a scan alone), "join_bounds"
+ * and "join_emit" (the two kernels of t9_join_count / t9_join_emit).
  * ------------------------------------------------------------------ */
 int t9_perf_enable(int on);
 int t9_perf_read(const char* kernel_class, double* total_ms,

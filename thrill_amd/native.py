@@ -98,6 +98,12 @@ _SIGS = {
     "t9_scan_u64": (i32, [vp, vp, vp, u64, i32, i32, i32, u64, vp, vp, vp]),
     "t9_scan_kv": (i32, [vp, vp, vp, u64, i32, i32, u64, vp, vp, vp]),
     "t9_fold_u64": (i32, [vp, vp, u64, u32, i32, i32, vp, vp, vp]),
+    "t9_join_geometry": (None, [ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                ctypes.POINTER(u32)]),
+    "t9_join_workspace": (u64, [u64, u64]),
+    "t9_join_count": (i32, [vp, vp, u64, vp, u64, ctypes.POINTER(u64), vp,
+                            vp]),
+    "t9_join_emit": (i32, [vp, u64, u64, vp, u64, vp, vp, vp]),
     "t9_text_tokenize_workspace": (u64, [u64]),
     "t9_text_tokenize": (i32, [vp, vp, u64, vp, vp, vp, vp, vp]),
     "t9_text_hash2": (i32, [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]),
@@ -217,6 +223,26 @@ class Native:
         t, p = u32(), u32()
         self._lib.t9_scan_geometry(ctypes.byref(t), ctypes.byref(p))
         return t.value, p.value
+
+    def join_geometry(self):
+        """(left keys per block of the bounds kernel, output positions per
+        block of the emit kernel, most right keys a bounds block stages in
+        LDS); no ctx argument, pure host code."""
+        lt, ot, sk = u32(), u32(), u32()
+        self._lib.t9_join_geometry(ctypes.byref(lt), ctypes.byref(ot),
+                                   ctypes.byref(sk))
+        return lt.value, ot.value, sk.value
+
+    def join_count(self, d_lkeys, n_left, d_rkeys, n_right, d_ws, stream):
+        """t9_join_count: match the two key arrays, leave the join state in
+        d_ws and return the number of result pairs."""
+        total = u64(0)
+        rc = self._lib.t9_join_count(self.ctx, d_lkeys, n_left, d_rkeys,
+                                     n_right, ctypes.byref(total), d_ws,
+                                     stream)
+        if rc != 0:
+            raise T9Error(f"t9_join_count failed rc={rc}")
+        return total.value
 
     def version(self):
         return self._lib.t9_version().decode()

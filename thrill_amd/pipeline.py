@@ -555,6 +555,120 @@ class PrefixSum:
         self.nat.close()
 
 
+def hash_partition_exchange(nat, dist, d_keys, arrays, n, rank, world):
+    """Send every item to rank Hash128to64(0, key) % world — the
+    reference's hash(key) % workers — with one all-to-all per array.
+    d_keys and every tensor of `arrays` (d_keys may be one of them) hold n
+    8-byte elements; item i is element i of each. Returns (received
+    tensors in the order of `arrays`, n_recv). The partition is stable and
+    the shares arrive ordered by source rank, so with world == 1 the
+    received arrays equal the sent ones."""
+    s = _stream()
+    p = world
+    d_bucket = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    d_counts = torch.empty(p, dtype=torch.int64, device="cuda")
+    nat.hash_bucket(_ptr(d_keys), n, 0, p, _ptr(d_bucket), _ptr(d_counts),
+                    s)
+    d_perm = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    d_offs = torch.empty(p + 1, dtype=torch.int64, device="cuda")
+    d_ws = torch.empty(max(int(nat.ws("partition_idx", n)), 256),
+                       dtype=torch.uint8, device="cuda")
+    nat.partition_idx(_ptr(d_bucket), n, p, _ptr(d_perm), _ptr(d_offs),
+                      _ptr(d_ws), s)
+    send_counts = d_counts.cpu().numpy().astype(np.int64)
+    recv_counts = exchange_counts(dist, send_counts, rank, world)
+    n_recv = int(recv_counts.sum())
+    exchange = os.environ.get("T9_EXCHANGE", "t9")
+    recv = []
+    for a in arrays:
+        g = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+        if n:
+            nat.gather_records(_ptr(a), _ptr(d_perm), n, 8, _ptr(g), s)
+        r = torch.empty(max(n_recv, 1), dtype=torch.int64, device="cuda")
+        if exchange == "t9" or world == 1:
+            a2a(nat, g, send_counts, r, recv_counts, 8)
+        else:
+            dist.all_to_all_single(
+                r[:n_recv], g[:n],
+                output_split_sizes=recv_counts.tolist(),
+                input_split_sizes=send_counts.tolist())
+        recv.append(r[:n_recv])
+    return recv, n_recv
+
+
+class InnerJoin:
+    """One rank's InnerJoin of (u64 key, 64-bit value) pairs, the
+    reference's JoinNode (api/inner_join.hpp) with the key extractors and
+    the join function applied by the caller: step() returns, for every pair
+    of a left and a right item with equal keys, the key and both values.
+    Single rank: t9_join_count, allocate, t9_join_emit, three gathers; the
+    rows are ordered by key, then left position, then right position.
+    world > 1 (or T9_FORCE_DIST): each side is hash-partitioned and
+    exchanged (hash_partition_exchange) and the rank joins its shares;
+    order across ranks is unspecified."""
+
+    def __init__(self, rank=0, world=1, device=0):
+        self.nat = Native(device=device, rank=rank, world=world)
+        self.rank, self.world = rank, world
+        if world > 1 and os.environ.get("T9_EXCHANGE", "t9") == "t9":
+            import torch.distributed as dist
+            bootstrap_comm(self.nat, dist, rank)
+
+    @staticmethod
+    def _check(d_keys, d_vals, side):
+        for t in (d_keys, d_vals):
+            if t.dim() != 1 or t.element_size() != 8 or \
+                    not t.is_contiguous():
+                raise T9Error(f"InnerJoin: {side} keys/vals must be "
+                              "contiguous 1-d tensors of 8-byte elements")
+        if d_keys.numel() != d_vals.numel():
+            raise T9Error(f"InnerJoin: {side} keys/vals differ in length")
+
+    def _join_local(self, lk, lv, rk, rv):
+        nat, s = self.nat, _stream()
+        nl, nr = lk.numel(), rk.numel()
+        d_ws = torch.empty(int(nat.ws("join", nl, nr)), dtype=torch.uint8,
+                           device="cuda")
+        m = nat.join_count(_ptr(lk) if nl else None, nl,
+                           _ptr(rk) if nr else None, nr, _ptr(d_ws), s)
+        keys = torch.empty(m, dtype=lk.dtype, device="cuda")
+        lvals = torch.empty(m, dtype=lv.dtype, device="cuda")
+        rvals = torch.empty(m, dtype=rv.dtype, device="cuda")
+        if m:
+            d_li = torch.empty(m, dtype=torch.int32, device="cuda")
+            d_ri = torch.empty(m, dtype=torch.int32, device="cuda")
+            nat.join_emit(nl, nr, _ptr(d_ws), m, _ptr(d_li), _ptr(d_ri), s)
+            nat.gather_records(_ptr(lk), _ptr(d_li), m, 8, _ptr(keys), s)
+            nat.gather_records(_ptr(lv), _ptr(d_li), m, 8, _ptr(lvals), s)
+            nat.gather_records(_ptr(rv), _ptr(d_ri), m, 8, _ptr(rvals), s)
+        return keys, lvals, rvals, m
+
+    def step(self, d_lkeys, d_lvals, d_rkeys, d_rvals):
+        """Join this rank's left and right pairs (device tensors of 8-byte
+        elements). Returns (keys, lvals, rvals, m): m rows, row r being
+        (key, left value, right value) of one matching pair."""
+        self._check(d_lkeys, d_lvals, "left")
+        self._check(d_rkeys, d_rvals, "right")
+        if self.world == 1 and not os.environ.get("T9_FORCE_DIST"):
+            return self._join_local(d_lkeys, d_lvals, d_rkeys, d_rvals)
+
+        import torch.distributed as dist
+        (lk, lv), _ = hash_partition_exchange(
+            self.nat, dist, d_lkeys, [d_lkeys, d_lvals], d_lkeys.numel(),
+            self.rank, self.world)
+        (rk, rv), _ = hash_partition_exchange(
+            self.nat, dist, d_rkeys, [d_rkeys, d_rvals], d_rkeys.numel(),
+            self.rank, self.world)
+        # received shares are int64 words: give them the callers' dtypes
+        return self._join_local(lk.view(d_lkeys.dtype),
+                                lv.view(d_lvals.dtype),
+                                rk.view(d_rkeys.dtype),
+                                rv.view(d_rvals.dtype))
+
+    def close(self):
+        self.nat.close()
+
+
 class TeraSort:
     """One rank's TeraSort state. world==1: pure local sort. world>1:
     sample -> splitters -> classify -> partition -> all-to-all -> local
