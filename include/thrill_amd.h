@@ -90,6 +90,16 @@ int t9_extract_key64_le(t9_context* ctx, const uint8_t* d_recs, uint64_t n,
                         uint32_t rec_size, uint32_t key_off,
                         uint64_t* d_keys, uint32_t* d_idx, void* stream);
 
+/* The fused first pass of the record sort on its own: the u64 key prefix of
+ * each record at offset 0 (big-endian, or native little-endian when le != 0),
+ * the record index iota unless d_idx is NULL, and d_hist[t * 256 + d] = the
+ * number of records of the 8192-record tile t whose top key byte is d
+ * (ceil(n / 8192) rows). rec_size is 100 or 128 (T9_EINVAL otherwise);
+ * d_recs is 4-byte aligned. */
+int t9_extract_key64_hist(t9_context* ctx, const uint8_t* d_recs, uint64_t n,
+                          uint32_t rec_size, int le, uint64_t* d_keys,
+                          uint32_t* d_idx, uint32_t* d_hist, void* stream);
+
 /* out[i] = recs[idx[i]] for fixed-size records; rec_size is a positive
  * multiple of 4 (T9_EINVAL otherwise, before any device call). */
 int t9_gather_records(t9_context* ctx, const uint8_t* d_recs,

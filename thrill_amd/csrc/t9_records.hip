@@ -560,6 +560,132 @@ static void launch_extract_hist(u32 rw, bool le, bool sb, u32 B,
                            dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
 }
 
+/* orders one wave's LDS writes before its own cross-lane LDS reads (and the
+ * reads before the next overwrite) without a block barrier: LDS serves a
+ * wave's operations in issue order, so only the compiler has to be held */
+__device__ inline void t9_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* The fused extract + pass-1 histogram with wave-private staging: same
+ * grid, same outputs as k_extract_hist, but each of the block's 4 waves
+ * owns a contiguous quarter of the tile (2048 records) and a private LDS
+ * slice of 64 records, so the steady state has no block barrier — a wave
+ * only ever needs the 64 records it extracts itself, and the histogram add
+ * is wave-local ballots plus LDS atomics. One barrier stands before the
+ * first use of s_cnt and one before hist is written.
+ * The records are read once and the keys are not read back by this kernel,
+ * so both go non-temporal: that, not the missing barriers, is what this
+ * form gains over k_extract_hist, and the block-staged
+ * form loses with the same hints. A whole sub-tile is RW unrolled loads per
+ * lane, all in flight before the first LDS write; the partial sub-tile at
+ * the end of the input goes word by word, guarded. */
+template <int RW, bool LE, bool IDX>
+__global__ __launch_bounds__(256) void k_extract_hist_wave(
+    const u8* __restrict__ recs, u64 n, u64* __restrict__ keys,
+    u32* __restrict__ idx, u32* __restrict__ hist) {
+    constexpr int SUBW = 64 * RW;              /* words per wave sub-tile */
+    __shared__ u32 s_buf[4][SUBW];
+    __shared__ u32 s_cnt[256];
+    const u32 tid = threadIdx.x;
+    const u32 lane = tid & 63;
+    const u32 wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u64 tile0 = (u64)blockIdx.x * 8192;
+    const u32 tn = (u32)((n - tile0 < 8192) ? (n - tile0) : 8192);
+    const u32 q0 = wv * 2048;                  /* this wave's quarter */
+    const u32 qn = (tn > q0) ? ((tn - q0 < 2048) ? tn - q0 : 2048) : 0;
+    const u32 nfull = qn >> 6;                 /* whole 64-record sub-tiles */
+    const u32 rem = qn & 63;
+    u32* sl = s_buf[wv];
+    const u32* rin = (const u32*)recs + (tile0 + q0) * RW;
+
+    auto consume = [&](u32 s0, bool valid) {
+        u64 k = 0;
+        if (valid) {
+            const u32 a = sl[lane * RW], b = sl[lane * RW + 1];
+            if (LE)
+                k = ((u64)b << 32) | a;
+            else
+                k = ((u64)__builtin_bswap32(a) << 32) | __builtin_bswap32(b);
+            const u64 gi = tile0 + q0 + s0 + lane;
+            __builtin_nontemporal_store(k, &keys[gi]);
+            if (IDX) idx[gi] = (u32)gi;
+        }
+        t9_hist_ballot_add<8>(s_cnt, (u32)(k >> 56), valid, lane);
+    };
+
+    s_cnt[tid] = 0;
+    __syncthreads();
+    for (u32 t = 0; t < nfull; ++t) {
+        const u32* src = rin + (u64)t * SUBW;
+        u32 r[RW];
+#pragma unroll
+        for (int j = 0; j < RW; ++j)
+            r[j] = __builtin_nontemporal_load(&src[j * 64 + lane]);
+#pragma unroll
+        for (int j = 0; j < RW; ++j) sl[j * 64 + lane] = r[j];
+        t9_wave_lds_sync();
+        consume(t * 64, true);
+        t9_wave_lds_sync();
+    }
+    if (rem) {
+        const u32 wn = rem * RW;
+        const u32* src = rin + (u64)nfull * SUBW;
+        for (u32 w = lane; w < wn; w += 64)
+            sl[w] = __builtin_nontemporal_load(&src[w]);
+        t9_wave_lds_sync();
+        consume(nfull * 64, lane < rem);
+    }
+    __syncthreads();
+    hist[(u64)blockIdx.x * 256 + tid] = s_cnt[tid];
+}
+
+/* launch ladder of the wave-private form: the same RW / LE cases as above */
+template <bool IDX>
+static void launch_extract_hist_wave(u32 rw, bool le, u32 B, hipStream_t s,
+                                     const u8* d_in, u64 n, u64* d_keys,
+                                     u32* d_idx, u32* hist) {
+    if (rw == 25 && !le)
+        hipLaunchKernelGGL((k_extract_hist_wave<25, false, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else if (rw == 25)
+        hipLaunchKernelGGL((k_extract_hist_wave<25, true, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else if (!le)
+        hipLaunchKernelGGL((k_extract_hist_wave<32, false, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+    else
+        hipLaunchKernelGGL((k_extract_hist_wave<32, true, IDX>), dim3(B),
+                           dim3(256), 0, s, d_in, n, d_keys, d_idx, hist);
+}
+
+/* the fused pass of the record sort: the wave-private form unless
+ * T9_EXTRACT_WAVE=0 asks for the block-staged k_extract_hist, under which
+ * T9_EXTRACT_SB keeps its meaning; both read per call */
+static void launch_extract_hist_any(bool widx, u32 rw, bool le, u32 B,
+                                    hipStream_t s, const u8* d_in, u64 n,
+                                    u64* d_keys, u32* d_idx, u32* hist) {
+    const char* we = getenv("T9_EXTRACT_WAVE");
+    if (!(we && we[0] == '0')) {
+        if (widx) launch_extract_hist_wave<true>(rw, le, B, s, d_in, n,
+                                                 d_keys, d_idx, hist);
+        else launch_extract_hist_wave<false>(rw, le, B, s, d_in, n, d_keys,
+                                             d_idx, hist);
+        return;
+    }
+    /* single-buffer default: 6 blocks/CU measured 2.447 vs 2.56 ms
+       (double-buffer, 3 blocks/CU) — occupancy beats the saved
+       barrier; T9_EXTRACT_SB=0 restores double buffering */
+    const char* sbe = getenv("T9_EXTRACT_SB");
+    const bool sb = !(sbe && sbe[0] == '0');
+    if (widx) launch_extract_hist<true>(rw, le, sb, B, s, d_in, n, d_keys,
+                                        d_idx, hist);
+    else launch_extract_hist<false>(rw, le, sb, B, s, d_in, n, d_keys, d_idx,
+                                    hist);
+}
+
 /* scatter-records experiment (gather-wall probe): read the input
  * SEQUENTIALLY (every line fetched once, fully used) and write each
  * word to its record's destination: out[inv[rec]]. Mirrors
@@ -661,6 +787,24 @@ int t9_extract_key64_le(t9_context* ctx, const u8* d_recs, u64 n,
                                     dim3(256), 0, (hipStream_t)stream,
                                     d_recs, n, rec_size / 4, key_off,
                                     d_keys, d_idx));
+    T9_LAUNCH_CHECK();
+    return T9_OK;
+}
+
+int t9_extract_key64_hist(t9_context* ctx, const u8* d_recs, u64 n,
+                          u32 rec_size, int le, u64* d_keys, u32* d_idx,
+                          u32* d_hist, void* stream) {
+    (void)ctx;
+    if (!d_recs || !d_keys || !d_hist) return T9_EINVAL;
+    if ((rec_size != 100 && rec_size != 128) || n >= (1ull << 32))
+        return T9_EINVAL;
+    if (n == 0) return T9_OK;
+    const u64 B = t9_ceil_div(n, 8192);
+    T9_PERF_WRAP((hipStream_t)stream, "extract",
+                 launch_extract_hist_any(d_idx != nullptr, rec_size / 4,
+                                         le != 0, (u32)B,
+                                         (hipStream_t)stream, d_recs, n,
+                                         d_keys, d_idx, d_hist));
     T9_LAUNCH_CHECK();
     return T9_OK;
 }
@@ -836,7 +980,8 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
      * (1) DEFAULT for MSB-dispatch sizes: fused extract+hist — one
      *     LDS-staged coalesced pass over the records writes keys, the
      *     index iota AND the MSB pass-1 byte-7 histogram
-     *     (k_extract_hist), so the standalone extract's strided loads
+     *     (k_extract_hist_wave; k_extract_hist under T9_EXTRACT_WAVE=0),
+     *     so the standalone extract's strided loads
      *     and the pass-1 histogram read both disappear. T9_EXTRACT_HIST=0
      *     disables.
      * (2) the round-1 per-lane fused path (T9_FUSED_EXTRACT=1): measured
@@ -870,23 +1015,14 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
     if (eh && !fused) {
         u32* hist = t9i_msb_pass1_hist(pair_ws, n);
         const u64 B = t9_ceil_div(n, 8192);
-        /* single-buffer default: 6 blocks/CU measured 2.447 vs 2.56 ms
-           (double-buffer, 3 blocks/CU) — occupancy beats the saved
-           barrier; T9_EXTRACT_SB=0 restores double buffering */
-        const char* sbe = getenv("T9_EXTRACT_SB");
-        const bool sb = !(sbe && sbe[0] == '0');
         /* the pass-1 scatter produces the index iota itself, so the
          * extract need not write it (0.43 GB written + 0.43 GB read back
          * at the 10 GiB bench); T9_EXTRACT_IOTA=1 restores the round trip */
         const char* ie = getenv("T9_EXTRACT_IOTA");
         const bool widx = ie && ie[0] == '1';
         T9_PERF_WRAP(s, "extract",
-                     if (widx) launch_extract_hist<true>(
-                         rw, le, sb, (u32)B, s, d_in, n, d_keys, d_idx,
-                         hist);
-                     else launch_extract_hist<false>(
-                         rw, le, sb, (u32)B, s, d_in, n, d_keys, d_idx,
-                         hist));
+                     launch_extract_hist_any(widx, rw, le, (u32)B, s, d_in,
+                                             n, d_keys, d_idx, hist));
         T9_LAUNCH_CHECK();
         /* 100-byte records through the default span gather may be
          * gathered chunk by chunk while the sub-bucket sort is still

@@ -54,6 +54,7 @@ _SIGS = {
     "t9_sort_pairs_workspace": (u64, [u64]),
     "t9_sort_pairs_u64_u32": (i32, [vp, vp, vp, u64, vp, vp]),
     "t9_extract_key64": (i32, [vp, vp, u64, u32, u32, vp, vp, vp]),
+    "t9_extract_key64_hist": (i32, [vp, vp, u64, u32, i32, vp, vp, vp, vp]),
     "t9_gather_records": (i32, [vp, vp, vp, u64, u32, vp, vp]),
     "t9_sort_records_workspace": (u64, [u64, u32]),
     "t9_sort_records": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
