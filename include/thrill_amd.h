@@ -161,6 +161,17 @@ int t9_sort_last_tiecount(const t9_context* ctx);
  * the same. */
 int t9_sort_last_fused(const t9_context* ctx);
 
+/* Whether the last t9_sort_records / t9_sort_records_keyle call on this
+ * context ran the packed form of pass 2 and of the fused kernel: one u64 per
+ * element, (key bits 46..10) << 27 | record index, used wherever the fused
+ * kernel runs and n <= 2^27. 1 = the packed run produced the output; 2 = it
+ * started, met a run of more than 8 records whose kept key bits agree, and
+ * pass 2 and the fused kernel ran again in the wide form (what
+ * t9_sort_last_fused and t9_sort_last_tiecount then report is that wide
+ * run); 0 = not used. T9_SORT_PACKED=0 keeps the wide form. The sorted
+ * output is the same. */
+int t9_sort_last_packed(const t9_context* ctx);
+
 /* ------------------------------------------------------------------ *
  * Classification + partition — replaces TransmitItems' tree-descent loop
  * (thrill/api/sort.hpp:434-535). bucket(item i) = #{ j : (splitter_key[j],

@@ -37,6 +37,7 @@ int t9_create(t9_context** out, int device, int rank, int world,
     ctx->last_schedule = 0;
     ctx->last_tiecount = 0;
     ctx->last_fused = 0;
+    ctx->last_packed = 0;
     *out = ctx;
     return T9_OK;
 }
@@ -86,6 +87,10 @@ int t9_sort_last_tiecount(const t9_context* ctx) {
 
 int t9_sort_last_fused(const t9_context* ctx) {
     return ctx ? ctx->last_fused : T9_EINVAL;
+}
+
+int t9_sort_last_packed(const t9_context* ctx) {
+    return ctx ? ctx->last_packed : T9_EINVAL;
 }
 
 /* ------------------------------------------------------------------ *

@@ -698,6 +698,204 @@ __global__ __launch_bounds__(64, 2) void k_wave16_sort_gather(
     }
 }
 
+/* ------------------------------------------------------------------ *
+ * k_wave16_sort_gather_packed: the same kernel over the packed pass-2
+ * output (k_scatter_seg9_packed): one u64 composite per element,
+ * C = (key bits 46..10) << T9_PK_IBITS | record index. C is already a
+ * stable sort key, so the block sorts the ns composites as they are: no
+ * position field, no index array to re-gather from, and nothing is written
+ * back but the records.
+ *
+ * The composite drops key bits 9..0, so neighbours with equal C >> IBITS
+ * are only CANDIDATE ties: true ones (equal 8-byte keys, to be ordered by
+ * bytes 8..99) or false ones (keys that differ in the dropped bits). Both
+ * are settled the same way: a candidate run of <= T9_FUSED_RUNMAX is
+ * insertion-sorted by the full order, the record's 64-bit key (big-endian,
+ * or native under keyle) and then its bytes 8..99, by swapping the index
+ * fields. The less is strict and a run starts in index order, so true
+ * duplicates keep input order. What the block cannot settle (a longer run)
+ * goes to *ntied and the block skips its gather; every block skips it once
+ * *ntied is non-zero. *ntied == 0 after the kernel means: out is complete.
+ * Otherwise the caller reruns pass 2 and the sort in the wide form.
+ * A pad is ~0; a live composite can equal it only at index 2^27 - 1 with
+ * all kept key bits set, and then the two are the same value wherever the
+ * merge puts them.
+ * ------------------------------------------------------------------ */
+__device__ __forceinline__ bool t9_rec100_less(
+    const u32* __restrict__ rin, u32 ra, u32 rb, bool keyle) {
+    const u32* a = rin + (u64)ra * 25;
+    const u32* b = rin + (u64)rb * 25;
+    const u32 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
+    const u64 ka = keyle ? (((u64)a1 << 32) | a0)
+                         : (((u64)__builtin_bswap32(a0) << 32) |
+                            __builtin_bswap32(a1));
+    const u64 kb = keyle ? (((u64)b1 << 32) | b0)
+                         : (((u64)__builtin_bswap32(b0) << 32) |
+                            __builtin_bswap32(b1));
+    if (ka != kb) return ka < kb;
+    return t9_rec100_tail_less(rin, ra, rb);
+}
+
+/* record index of a composite. It is below n by construction; the clamp to
+ * imax = n - 1 keeps a damaged workspace from becoming a wild read. */
+__device__ __forceinline__ u32 t9_pk_idx(u64 c, u32 imax) {
+    const u32 i = (u32)c & T9_PK_IMASK;
+    return i < imax ? i : imax;
+}
+
+template <int D>
+__global__ __launch_bounds__(64, 2) void k_wave16_sort_gather_packed(
+    const u64* __restrict__ comp, const u32* __restrict__ sub_start,
+    const u32* __restrict__ sub_n, u32* ntied, const u32* __restrict__ rin,
+    u32* __restrict__ rout, u32 keyle, u32 imax) {
+    constexpr int NSORT = 1024, BLOCK = 64, E = 16, ROUNDS = 6, RW = 25;
+    constexpr int IB = T9_PK_IBITS;
+    __shared__ __attribute__((aligned(16))) u64 lc[NSORT];
+    __shared__ u32 s_ntie;
+    __shared__ u32 s_settled;
+
+    const u32 sb = blockIdx.x;
+    const u32 ns = sub_n[sb];
+    if (ns == 0 || ns > (u32)NSORT) return;
+    const u32 gbase = sub_start[sb];
+    const u32 lane = threadIdx.x;
+    const u32 e0 = lane * E;
+    u32* const ob = rout + (u64)gbase * RW;
+    const u64* const cb = comp + gbase;
+
+    if (ns == 1) {
+        if (__hip_atomic_load(ntied, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        const u32 idx = t9_pk_idx(cb[0], imax);
+        if (lane < (u32)RW) ob[lane] = rin[(u64)idx * RW + lane];
+        return;
+    }
+
+    if (lane == 0) { s_ntie = 0; s_settled = 0; }
+
+    u64 c[E];
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        /* unconditional at a clamped position, so that the 16 loads are
+         * in flight together and not one per branch */
+        const u64 cc = cb[p < ns ? p : ns - 1];
+        lc[t9_w16_phys(p)] = (p < ns) ? cc : ~0ull;
+    }
+    __syncthreads();
+    t9_w16_row_load(lc, lane, c);
+
+    t9_w16_blocksort<E, ROUNDS>(lc, lane, c);
+
+    __syncthreads();
+    t9_w16_row_store(lc, lane, c);
+    __syncthreads();
+    {
+        const u64 nxt = (e0 + E < (u32)NSORT) ? lc[t9_w16_phys(e0 + E)]
+                                              : ~0ull;
+        u32 cnt = 0;
+#pragma unroll
+        for (int r = 0; r < E; ++r) {
+            const u64 hi = (r + 1 < E) ? c[r + 1] : nxt;
+            cnt += (e0 + r + 1 < ns) && ((c[r] >> IB) == (hi >> IB));
+        }
+        if (cnt) atomicAdd(&s_ntie, cnt);
+    }
+    __syncthreads();
+    const u32 nt = s_ntie;   /* candidate neighbours, settled or not */
+    if (nt) {
+        /* each lane settles the runs that START among its 16 elements;
+         * runs are disjoint, and the swaps leave the key bits that the
+         * scans compare alone */
+        u32 settled = 0;
+#pragma unroll 1
+        for (u32 e = e0; e < e0 + E && e + 1 < ns; ++e) {
+            const u64 key = lc[t9_w16_phys(e)] >> IB;
+            if ((lc[t9_w16_phys(e + 1)] >> IB) != key) continue;
+            if (e > 0 && (lc[t9_w16_phys(e - 1)] >> IB) == key) continue;
+            u32 len = 2;
+            while (len <= T9_FUSED_RUNMAX && e + len < ns &&
+                   (lc[t9_w16_phys(e + len)] >> IB) == key)
+                ++len;
+            if (len > T9_FUSED_RUNMAX) continue;   /* left to the wide redo */
+            for (u32 i = 1; i < len; ++i)
+                for (u32 j = i; j > 0; --j) {
+                    const u32 hi_at = t9_w16_phys(e + j);
+                    const u32 lo_at = t9_w16_phys(e + j - 1);
+                    const u64 ch = lc[hi_at], cl = lc[lo_at];
+                    const u32 ih = (u32)ch & T9_PK_IMASK;   /* swapped as is */
+                    const u32 il = (u32)cl & T9_PK_IMASK;
+                    if (!t9_rec100_less(rin, ih < imax ? ih : imax,
+                                        il < imax ? il : imax, keyle != 0))
+                        break;
+                    lc[hi_at] = (ch & ~(u64)T9_PK_IMASK) | il;
+                    lc[lo_at] = (cl & ~(u64)T9_PK_IMASK) | ih;
+                }
+            settled += len - 1;
+        }
+        if (settled) atomicAdd(&s_settled, settled);
+    }
+    __syncthreads();
+    /* the sorted record indices */
+    u32 v[E];
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        v[r] = t9_pk_idx(lc[t9_w16_phys(p)], imax);
+    }
+    const u32 unsettled = nt - s_settled;
+    if (lane == 0 && unsettled) atomicAdd(ntied, unsettled);
+    if (unsettled) return;   /* the wide redo produces the output */
+
+    /* ---- gather phase: lc becomes the index buffer ---- */
+    __syncthreads();
+    u32* const li = (u32*)lc;
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        const u32 p = lane + (u32)BLOCK * r;
+        if (p < ns) li[p] = v[r];
+    }
+    __syncthreads();
+    if (__hip_atomic_load(ntied, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        return;
+    /* the word loop of k_wave16_sort_gather. The word index is made
+     * opaque once per trip: left to itself the compiler widens it to 64
+     * bits and carries the 16 divisions by 25 across the loop in 64-bit
+     * registers (130 VGPRs against 76). */
+    const u32 W = ns * RW;
+    for (u32 gb = 0; gb < W; gb += (u32)BLOCK * D) {
+        u32 g0 = gb + lane;
+        asm volatile("" : "+v"(g0));
+        u32 x[D];
+        if (gb + (u32)BLOCK * D <= W) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const u32 g = g0 + (u32)BLOCK * j;
+                const u32 rec = g / (u32)RW;
+                x[j] = rin[(u64)li[rec] * RW + (g - rec * RW)];
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) ob[g0 + (u32)BLOCK * j] = x[j];
+        }
+        else {
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const u32 g = g0 + (u32)BLOCK * j;
+                if (g < W) {
+                    const u32 rec = g / (u32)RW;
+                    x[j] = rin[(u64)li[rec] * RW + (g - rec * RW)];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const u32 g = g0 + (u32)BLOCK * j;
+                if (g < W) ob[g] = x[j];
+            }
+        }
+    }
+}
+
 /* wave16 span sort (3-level path, PASSES=6 spans): same blocksort as
  * k_wave16_sort_sub, but out-of-place over span descriptors. Valid for
  * the 6-pass span case only: spans pack (b7,b6,b5) groups that share

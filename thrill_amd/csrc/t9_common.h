@@ -60,7 +60,15 @@ struct t9_context {
     int last_schedule;   /* t9_sort_last_schedule */
     int last_tiecount;   /* t9_sort_last_tiecount */
     int last_fused;      /* t9_sort_last_fused */
+    int last_packed;     /* t9_sort_last_packed */
 };
+
+/* packed record sort (9-bit two-level flow, n <= 2^T9_PK_IBITS): after
+ * pass 2 an element is one u64, (key bits 46..10) << T9_PK_IBITS | index.
+ * Key bits 63..47 are implied by the sub-bucket; 64 - 27 = 37 of the other
+ * 47 fit, and the 10 dropped ones are settled from the record itself. */
+#define T9_PK_IBITS 27
+#define T9_PK_IMASK ((1u << T9_PK_IBITS) - 1u)
 
 /* record-sort request riding along the pair sort: when the two-level
  * 9-bit MSB flow can, it gathers out[a..b) = recs[idx[a..b)] chunk by
@@ -77,6 +85,9 @@ struct t9_overlap_req {
     u32 rec_words;
     u32 chunks;   /* out: non-empty chunks gathered on the internal stream */
     u32 fused;    /* out: 1 = the fused sort + gather kernel ran */
+    u32 keyle;    /* in: the record key is a native little-endian u64 */
+    u32 packed;   /* out: 1 = pass 2 and the fused kernel ran in packed form
+                   * (d_keys holds composites, d_vals was not written) */
 };
 
 /* splitmix64 random access — must match oracle/t9_oracle.cpp splitmix64_at */

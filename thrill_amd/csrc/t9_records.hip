@@ -14,6 +14,9 @@
 #include <vector>
 #include <algorithm>
 
+extern "C" int t9i_sort_pairs_msb_unpacked_redo(u64*, u32*, u64, void*,
+                                                void*, t9_overlap_req*,
+                                                u32*);
 extern "C" int t9i_count_tied(const u64* d_keys, u64 n, u32* d_ntied,
                               hipStream_t s);
 extern "C" u64 t9_sort_pairs_workspace(u64 n);
@@ -1000,7 +1003,7 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
     bool fused = fe && atoi(fe) && n >= (1ull << 14) &&
                  (rec_size == 100 || rec_size == 128);
     int rc;
-    t9_overlap_req ov = { nullptr, nullptr, 0, 0, 0 };
+    t9_overlap_req ov = { nullptr, nullptr, 0, 0, 0, le ? 1u : 0u, 0 };
     /* 1: the sub-bucket sort counted the ties into d_ntied itself; then
      * d_keys is sorted only inside sub-buckets that hold a tie (see
      * k_wave16_sort_sub), which is all its readers below need: k_tie_flags
@@ -1011,6 +1014,7 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
         ctx->last_schedule = 0;
         ctx->last_tiecount = 0;
         ctx->last_fused = 0;
+        ctx->last_packed = 0;
     }
     if (eh && !fused) {
         u32* hist = t9i_msb_pass1_hist(pair_ws, n);
@@ -1064,6 +1068,22 @@ static int sort_records_impl(t9_context* ctx, const u8* d_in, u8* d_out,
     u32 ntied = 0;
     HIP_TRY(hipMemcpyAsync(&ntied, d_ntied, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (ov.packed) {
+        /* packed pass 2 + fused kernel (n <= 2^27): nothing left over means
+         * d_out is complete. Otherwise some candidate run was too long for
+         * its block: pass 2 and the fused kernel run again in the wide form
+         * (pass 1's output is intact) and everything below sees what a wide
+         * run leaves, its own tie count included. */
+        ctx->last_packed = ntied ? 2 : 1;
+        if (ntied) {
+            rc = t9i_sort_pairs_msb_unpacked_redo(d_keys, d_idx, n, pair_ws,
+                                                  stream, &ov, d_ntied);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(&ntied, d_ntied, 4,
+                                   hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
     if (ov.chunks) {
         ctx->last_schedule = (int)ov.chunks;
         /* no tie: every chunk's gather ran to the end (d_ntied only

@@ -49,6 +49,9 @@ extern "C" void t9i_launch_seg_scan9(u32, void*, u32*, const u32*,
 extern "C" void t9i_launch_scatter_seg9(u32, int, void*, const u64*,
                                         const u32*, const u32*, const u32*,
                                         u64*, u32*, const u32*);
+extern "C" void t9i_launch_scatter_seg9_packed(u32, void*, const u64*,
+                                               const u32*, const u32*,
+                                               const u32*, u64*, const u32*);
 constexpr u64 NSUB9 = 256ull * 512;
 
 /* level-2 digit width: 9 bits by default (measured -1.5% end to end:
@@ -1095,6 +1098,34 @@ static bool t9i_fused_gather() {
     return e[0] != '0';
 }
 
+/* Packed record sort (k_scatter_seg9_packed + k_wave16_sort_gather_packed):
+ * one u64 composite per element after pass 2 where the fused kernel runs
+ * and the record index fits T9_PK_IBITS bits. On by default (DESIGN.md
+ * §Measurement Round 9); T9_SORT_PACKED=0 keeps the wide (u64 key, u32
+ * index) form. T9_SORT_PACKED_IDXBITS (test hook, at most T9_PK_IBITS)
+ * lowers the bound on n so that a small input can sit on either side of
+ * it; the composite layout stays the same. */
+static bool t9i_packed_ok(u64 n) {
+    const char* e = getenv("T9_SORT_PACKED");
+    if (e && e[0] == '0') return false;
+    u32 bits = T9_PK_IBITS;
+    const char* b = getenv("T9_SORT_PACKED_IDXBITS");
+    if (b && b[0]) {
+        const int v = atoi(b);
+        if (v >= 1 && v < (int)T9_PK_IBITS) bits = (u32)v;
+    }
+    return n <= (1ull << bits);
+}
+
+static void t9i_launch_fused_wide(hipStream_t s, u64* d_keys, u32* d_vals,
+                                  const u32* sub_start, const u32* sub_n,
+                                  u32* tcount, const t9_overlap_req* ov) {
+    hipLaunchKernelGGL(
+        (k_wave16_sort_gather<T9_FUSED_D, T9_FUSED_TIES != 0>),
+        dim3((u32)NSUB9), dim3(64), 0, s, d_keys, d_vals, sub_start, sub_n,
+        tcount, (const u32*)ov->recs, (u32*)ov->out);
+}
+
 /* out[0..1] = info[0..1] (k_subinfo's max and oversize count), out[1 + c]
  * = first record of chunk c (c = 1..K-1): one read-back fetches all.
  * sub_start is a running exclusive sum over the sub-buckets (k_seg_scan9:
@@ -1171,12 +1202,6 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                                               w.hist));
             t9i_launch_seg_scan9(256, stream, w.hist, w.abase, w.bucket_n,
                                  w.true_base, w.sub_start, w.sub_n);
-            T9_PERF_WRAP(s, "pair_scatter",
-                         t9i_launch_scatter_seg9((u32)B2, HAS_VAL, stream,
-                                                 w.alt_k, w.alt_v, w.abase,
-                                                 w.bucket_n, d_keys,
-                                                 d_vals, w.hist));
-            T9_LAUNCH_CHECK();
             HIP_TRY(hipMemsetAsync(w.ovr, 0, 8, s));
             hipLaunchKernelGGL(k_subinfo, dim3((u32)(NSUB9 / 256)),
                                dim3(256), 0, s, w.sub_n, (u32)NSUB9,
@@ -1212,6 +1237,31 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                     if (tie_counted) *tie_counted = 1;
                 }
             }
+            /* fused sort + gather (k_wave16_sort_gather): wherever the
+             * chunked schedule could have run, was not asked for, and the
+             * 1024 tier holds every sub-bucket. Event timing keeps the two
+             * stand-alone kernels so that their classes stay measurable.
+             * Known before pass 2, so that pass 2 can emit the packed
+             * composites where the packed fused kernel will read them. */
+            bool fuse = false, packed = false;
+            if constexpr (HAS_VAL) {
+                fuse = tcount && ov && ctx && !t9perf_on() && ov->recs &&
+                       ov->rec_words == 25 && overlap_chunks() == 0 &&
+                       maxsub <= 1024 && t9i_fused_gather();
+                packed = fuse && t9i_packed_ok(n);
+            }
+            if (packed)
+                t9i_launch_scatter_seg9_packed((u32)B2, stream, w.alt_k,
+                                               w.alt_v, w.abase, w.bucket_n,
+                                               d_keys, w.hist);
+            else
+                T9_PERF_WRAP(s, "pair_scatter",
+                             t9i_launch_scatter_seg9((u32)B2, HAS_VAL,
+                                                     stream, w.alt_k,
+                                                     w.alt_v, w.abase,
+                                                     w.bucket_n, d_keys,
+                                                     d_vals, w.hist));
+            T9_LAUNCH_CHECK();
             if (K && tcount) {
                 u64 bnd[T9_OVERLAP_MAXK + 1];
                 bnd[0] = 0;
@@ -1251,21 +1301,21 @@ static int sort_msb_impl(t9_context* ctx, const u64* pass1_src,
                     return T9_OK;
                 }
             }
-            /* fused sort + gather (k_wave16_sort_gather): wherever the
-             * chunked schedule could have run, was not asked for, and the
-             * 1024 tier holds every sub-bucket. Event timing keeps the two
-             * stand-alone kernels so that their classes stay measurable. */
             if constexpr (HAS_VAL) {
-                if (tcount && ov && ctx && !t9perf_on() && ov->recs &&
-                    ov->rec_words == 25 && overlap_chunks() == 0 &&
-                    maxsub <= 1024 && t9i_fused_gather()) {
-                    hipLaunchKernelGGL(
-                        (k_wave16_sort_gather<T9_FUSED_D, T9_FUSED_TIES != 0>),
-                        dim3((u32)NSUB9), dim3(64), 0, s, d_keys, d_vals,
-                        w.sub_start, w.sub_n, tcount, (const u32*)ov->recs,
-                        (u32*)ov->out);
+                if (fuse) {
+                    if (packed)
+                        hipLaunchKernelGGL(
+                            (k_wave16_sort_gather_packed<T9_FUSED_D>),
+                            dim3((u32)NSUB9), dim3(64), 0, s, d_keys,
+                            w.sub_start, w.sub_n, tcount,
+                            (const u32*)ov->recs, (u32*)ov->out, ov->keyle,
+                            (u32)(n - 1));
+                    else
+                        t9i_launch_fused_wide(s, d_keys, d_vals, w.sub_start,
+                                              w.sub_n, tcount, ov);
                     T9_LAUNCH_CHECK();
                     ov->fused = 1;
+                    ov->packed = packed ? 1 : 0;
                     return T9_OK;   /* tcount implies novr9 == 0 */
                 }
             }
@@ -1596,6 +1646,31 @@ extern "C" int t9i_sort_pairs_msb_ph(t9_context* ctx, u64* d_keys,
     return sort_msb_impl<true>(ctx, d_keys, d_keys, d_vals, n, d_workspace,
                                stream, true, ov, iota_vals != 0, d_ntied,
                                tie_counted);
+}
+
+/* After a packed run that left *d_ntied non-zero (a candidate run too long
+ * for the block): pass 1's output (alt_k, alt_v) and the pass-2 offsets in
+ * the workspace are untouched, so pass 2 and the fused kernel are rerun in
+ * the wide form on the same stream. d_keys, d_vals and *d_ntied are then
+ * what a wide run leaves, for the caller's tie path. */
+extern "C" int t9i_sort_pairs_msb_unpacked_redo(u64* d_keys, u32* d_vals,
+                                                u64 n, void* d_workspace,
+                                                void* stream,
+                                                t9_overlap_req* ov,
+                                                u32* d_ntied) {
+    hipStream_t s = (hipStream_t)stream;
+    MsbWs w = carve_msb((char*)d_workspace, n);
+    const u64 B2 = t9_ceil_div(n, T9_MSB_TILE) + 256;
+    HIP_TRY(hipMemsetAsync(d_ntied, 0, 4, s));
+    t9i_launch_scatter_seg9((u32)B2, 1, stream, w.alt_k, w.alt_v, w.abase,
+                            w.bucket_n, d_keys, d_vals, w.hist);
+    T9_LAUNCH_CHECK();
+    t9i_launch_fused_wide(s, d_keys, d_vals, w.sub_start, w.sub_n, d_ntied,
+                          ov);
+    T9_LAUNCH_CHECK();
+    ov->fused = 1;
+    ov->packed = 0;
+    return T9_OK;
 }
 
 extern "C" u32* t9i_msb_pass1_hist(void* d_workspace, u64 n) {

@@ -12,6 +12,10 @@
  * u16 count rows; digit-of-slot is recomputed from the staged key
  * instead of stored. Shares the pass-1 machinery and fallbacks with
  * t9_sort_msb.hip via its exported helpers.
+ *
+ * k_scatter_seg9_packed is the scatter of the packed record sort (n <= 2^27,
+ * fused sort + gather): one u64 composite per element instead of the
+ * (u64 key, u32 index) pair, one trip through the reorder buffer.
  */
 
 #include "t9_common.h"
@@ -345,9 +349,220 @@ __global__ __launch_bounds__(1024, 8) void k_scatter_seg9(
     }
 }
 
+/* Packed form of k_scatter_seg9 for the record sort whose sub-bucket sort
+ * also gathers (k_wave16_sort_gather_packed) and n <= 2^27. After this pass
+ * the top 17 key bits are implied by the sub-bucket, so one u64 per element
+ * is enough: C = (key bits 46..10) << 27 | idx, itself a stable sort key
+ * (the index breaks ties of the kept bits in input order). out_comp takes
+ * the place of out_keys; no value array is written.
+ *
+ * Ranking, the tile order, the bucket search and the 80 KiB / two blocks
+ * per CU are those of the wide form. The composite goes through the 64 KiB
+ * buffer once; it no longer holds the digit, so the digit of each slot
+ * travels next to it in bytes that are dead by then:
+ *
+ *   s_raw    composites from barrier C (the one reorder round) to the end;
+ *   s_wtot   s_raw[0, 32): as in the wide form;
+ *   s_wcnt   counts and tile positions up to barrier D;
+ *   s_delta  s_wcnt bytes [0, 2048): written between D and E, read after E;
+ *   s_dig8   s_wcnt bytes [2048, 10240): low 8 digit bits of every slot,
+ *            written between D and E by the lane that placed the slot;
+ *   s_hi     s_wcnt bytes [10240, 10244): tile position of digit 256's run.
+ *            The reordered tile is sorted by digit, so slot j has digit bit
+ *            8 set exactly where j >= s_hi.
+ */
+__global__ __launch_bounds__(1024, 8) void k_scatter_seg9_packed(
+    const u64* __restrict__ in_keys, const u32* __restrict__ in_vals,
+    const u32* __restrict__ abase, const u32* __restrict__ bucket_n,
+    u64* __restrict__ out_comp, const u32* __restrict__ offs) {
+    constexpr int TILE = T9_MSB_TILE;
+    constexpr int NW = 16;
+    constexpr int SUB = TILE / NW;
+    constexpr int GROUPS = SUB / 64;
+    __shared__ __align__(16) u8 s_raw[TILE * 8];
+    u64* const s_ocomp = (u64*)s_raw;
+    static_assert(SUB <= 65535 && TILE <= 65535, "u16 counts and offsets");
+    static_assert(NW * 64 == 1024 && NDIG9 == 8 * 64,
+                  "one thread per key column, waves 0..7 own the digits");
+    __shared__ __align__(16) u16 s_wcnt[NW * NDIG9];
+    u32* const s_wtot = (u32*)s_raw;
+    u32* const s_delta = (u32*)s_wcnt;
+    u8* const s_dig8 = (u8*)s_wcnt + NDIG9 * 4;
+    u32* const s_hi = (u32*)((u8*)s_wcnt + NDIG9 * 4 + TILE);
+    static_assert(NDIG9 * 4 + TILE + 4 <= NW * NDIG9 * 2,
+                  "the overlays fit the count array");
+
+    const u32 tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    /* tile order: see k_scatter_seg9 */
+    const u32 xper = gridDim.x >> 3, xrem = gridDim.x & 7;
+    const u32 xcd = blockIdx.x & 7;
+    const u32 tile = xcd * xper + (xcd < xrem ? xcd : xrem) +
+                     (blockIdx.x >> 3);
+    const u64 tbase64 = (u64)tile * TILE;
+    if (tbase64 >= abase[256]) return;
+    const u32 tbase = (u32)tbase64;
+
+    /* keys, indices, abase and bucket_n in one round of loads; a tile below
+     * abase[256] lies inside the padded pass-1 arrays whole */
+    const u32 wbase = wave * SUB;
+    u64 key[GROUPS];
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g)
+        key[g] = in_keys[tbase + wbase + g * 64 + lane];
+    u32 val[GROUPS];
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g)
+        val[g] = in_vals[tbase + wbase + g * 64 + lane];
+    u32 ab[4], bnq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        ab[q] = abase[q * 64 + lane];
+        bnq[q] = bucket_n[q * 64 + lane];
+    }
+    u16* const wc = s_wcnt + wave * NDIG9;
+    for (u32 t = lane; t < NDIG9; t += 64) wc[t] = 0;
+
+    u32 nle = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        nle += (u32)__popcll(__ballot(ab[q] <= tbase));
+    const u32 b = nle - 1, bq = b >> 6;
+    const u32 ab_b = (u32)__builtin_amdgcn_readlane(
+        (int)(bq == 0 ? ab[0] : bq == 1 ? ab[1] : bq == 2 ? ab[2] : ab[3]),
+        (int)(b & 63));
+    const u32 bn = (u32)__builtin_amdgcn_readlane(
+        (int)(bq == 0 ? bnq[0] : bq == 1 ? bnq[1] : bq == 2 ? bnq[2]
+                                                            : bnq[3]),
+        (int)(b & 63));
+    const u32 off_in_bucket = tbase - ab_b;
+    const u32 tn = (bn > off_in_bucket)
+                       ? ((bn - off_in_bucket < (u32)TILE)
+                              ? bn - off_in_bucket
+                              : (u32)TILE)
+                       : 0;
+    if (tn == 0) return;   /* block-uniform */
+
+    /* ranks and tile positions two to a register as in the wide form, and
+     * so the digits: once the composites are formed the keys are gone */
+    u32 pos2[GROUPS / 2] = {};
+    u32 dig2[GROUPS / 2] = {};
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+        const u32 i = wbase + g * 64 + lane;
+        const bool valid = i < tn;
+        const u32 d = (u32)(key[g] >> 47) & 511u;
+        u32 dlo = 0, dhi = 0;
+#pragma unroll
+        for (int bit = 0; bit < 9; ++bit) {
+            const u32 own = 0u - ((d >> bit) & 1u);
+            const u64 bb = __ballot(own != 0);
+            dlo |= (u32)bb ^ own;
+            dhi |= (u32)(bb >> 32) ^ own;
+        }
+        const u64 m = __ballot(valid) & ~(((u64)dhi << 32) | dlo);
+        const u32 wr = (u32)__popcll(m & ((1ull << lane) - 1ull));
+        const u32 before = wc[d];
+        pos2[g >> 1] |= (before + wr) << (16 * (g & 1));
+        dig2[g >> 1] |= d << (16 * (g & 1));
+        if (valid && wr == 0) wc[d] = (u16)(before + (u32)__popcll(m));
+        /* the composite, in the key's registers. Formed here and pinned:
+         * moved down to its use it would keep the index alive next to the
+         * key, and 8 of those do not fit. */
+        key[g] = (((key[g] << 17) >> T9_PK_IBITS) << T9_PK_IBITS) |
+                 (u64)val[g];
+        asm volatile("" : "+v"(key[g]));
+    }
+    /* and the digits are taken from dig2 again where they are wanted, not
+     * kept one to a register from here on */
+#pragma unroll
+    for (int q = 0; q < GROUPS / 2; ++q)
+        asm volatile("" : "+v"(dig2[q]), "+v"(pos2[q]));
+    u32 goff = 0;
+    if (tid < NDIG9) goff = offs[(u64)tile * NDIG9 + tid];
+    __syncthreads();                                   /* A */
+
+    u32 excl = 0;
+    if (tid < NDIG9) {
+        u32 run = 0;
+        for (int w = 0; w < NW; ++w) {
+            const u32 c = s_wcnt[w * NDIG9 + tid];
+            s_wcnt[w * NDIG9 + tid] = (u16)run;
+            run += c;
+        }
+        u32 v = run;
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 y = __shfl_up(v, off);
+            if (lane >= (u32)off) v += y;
+        }
+        excl = v - run;
+        if (lane == 63) s_wtot[wave] = v;
+    }
+    __syncthreads();                                   /* B */
+    u32 delta = 0, start = 0;
+    if (tid < NDIG9) {
+        start = excl;   /* tile position of the digit's run */
+        for (u32 w = 0; w < wave; ++w) start += s_wtot[w];
+        for (int w = 0; w < NW; ++w)
+            s_wcnt[w * NDIG9 + tid] += (u16)start;
+        delta = goff - start;
+    }
+    __syncthreads();                                   /* C */
+
+    /* the one reorder round. The LDS reads run for a whole tile, only the
+     * writes are conditional. */
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+        const u32 i = wbase + g * 64 + lane;
+        const u32 d = (dig2[g >> 1] >> (16 * (g & 1))) & 511u;
+        const u32 w = (u32)wc[d];
+        const u32 pos = ((pos2[g >> 1] >> (16 * (g & 1))) & 0xffffu) + w;
+        if (i < tn) s_ocomp[pos] = key[g];
+        pos2[g >> 1] += w << (16 * (g & 1));
+    }
+    __syncthreads();                                   /* D */
+    if (tid < NDIG9) s_delta[tid] = delta;
+    if (tid == 256) *s_hi = start;
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+        const u32 i = wbase + g * 64 + lane;
+        if (i < tn)
+            s_dig8[(pos2[g >> 1] >> (16 * (g & 1))) & 0xffffu] =
+                (u8)(dig2[g >> 1] >> (16 * (g & 1)));
+    }
+    __syncthreads();                                   /* E */
+
+    /* slot j = c * 1024 + tid of the reordered tile and its output position
+     * (below the end of the output array, as in the wide form). Past tn the
+     * digit byte is whatever the counts left there: it indexes s_delta in
+     * range and the position is not used. */
+    const u32 hi = *s_hi;
+    u64 k[GROUPS];
+    u32 gpos[GROUPS];
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c) k[c] = s_ocomp[c * 1024 + tid];
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c) {
+        const u32 j = c * 1024 + tid;
+        const u32 d = (u32)s_dig8[j] | (j >= hi ? 256u : 0u);
+        gpos[c] = s_delta[d] + j;
+    }
+#pragma unroll
+    for (int c = 0; c < GROUPS; ++c)
+        if (c * 1024 + tid < tn) out_comp[gpos[c]] = k[c];
+}
+
 /* C wrappers so the host flow in t9_sort_msb.hip can launch these
  * without cross-TU template plumbing */
 extern "C" {
+
+void t9i_launch_scatter_seg9_packed(u32 grid, void* stream,
+                                    const u64* in_keys, const u32* in_vals,
+                                    const u32* abase, const u32* bucket_n,
+                                    u64* out_comp, const u32* offs) {
+    hipLaunchKernelGGL(k_scatter_seg9_packed, dim3(grid), dim3(1024), 0,
+                       (hipStream_t)stream, in_keys, in_vals, abase,
+                       bucket_n, out_comp, offs);
+}
 
 void t9i_launch_hist_seg9(u32 grid, void* stream, const u64* keys,
                           const u32* abase, const u32* bucket_n,

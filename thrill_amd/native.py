@@ -62,6 +62,7 @@ _SIGS = {
     "t9_sort_last_schedule": (i32, [vp]),
     "t9_sort_last_tiecount": (i32, [vp]),
     "t9_sort_last_fused": (i32, [vp]),
+    "t9_sort_last_packed": (i32, [vp]),
     "t9_extract_key64_le": (i32, [vp, vp, u64, u32, u32, vp, vp, vp]),
     "t9_classify_u64": (i32, [vp, vp, u64, u64, vp, vp, u32, vp, vp, vp]),
     "t9_classify_rec": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, u32, u32,
@@ -190,6 +191,15 @@ class Native:
         k = self._lib.t9_sort_last_fused(self.ctx)
         if k < 0:
             raise T9Error(f"t9_sort_last_fused failed rc={k}")
+        return k
+
+    def sort_last_packed(self):
+        """1 = the packed pass 2 + fused kernel produced the output of the
+        last record sort; 2 = they started and the wide form redid it; 0 =
+        not used."""
+        k = self._lib.t9_sort_last_packed(self.ctx)
+        if k < 0:
+            raise T9Error(f"t9_sort_last_packed failed rc={k}")
         return k
 
     # perf registry functions take no context argument
